@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BA update iterations/s (+ correlation-lookup Gpix/s) of the MI355X hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one Gauss-Newton iteration of `droid_backends.ba` (linearise -> depth-side reduce ->
@@ -9,16 +9,25 @@ Schur complement -> Cholesky solve -> retraction) on synthetic data that is resi
 the clock starts.  K steps are timed as ONE ba call with iterations=K (what
 BASELINE.md section 3 defines: iters/s = K / wall(ba(iterations=K))).
 
+A plain run sets up, warms up (one ba call with iterations=W), times the K steps and prints the headline
+line.  --full adds everything else: the per-stage profile, the production call shape (iterations=2), the
+other configs / the weak-scaling figure (`extra`), the correlation operators (`corr`), the CPU baselines
+and the rooflines; --no-extra / --no-corr / --no-cpu-baseline drop parts of it again.
+
+--dump-outputs DIR writes what the timed call returned to its caller, the state after its last step, as
+DIR/poses.npy ([nbuf,7] float32) and DIR/disps.npy ([nbuf,H,W] float32, every rank's frames gathered).
+The inputs are seeded: the same arguments give the same inputs on every run.
+
 N = 1 : BASELINE.json configs[2], the graph the metric is quoted on (256 keyframes / 2000 edges,
-        48x64, lm=1e-5, ep=1e-2).  `extra.configs_1gpu` adds configs[1] (64 kf / 512 e), configs[3]
+        48x64, lm=1e-5, ep=1e-2).  With --full, `extra.configs_1gpu` adds configs[1] (64 kf / 512 e), configs[3]
         unsharded (256 kf / 8000 e) and configs[4] (stereo 96x128, 128 kf / 1024 e) on the same GPU.
 N > 1 : BASELINE.json configs[3]: 256 keyframes / 8000 edges IN TOTAL (--edges-total), sharded by source
         frame over the N ranks (droid_backends/ba_driver.py), one all-reduce (RCCL) of the packed lower
         triangle of the (6P+1)^2 fp64 reduced camera system per iteration, replicated solve.  Total work is
         fixed as N grows ("scaling": "strong").  `value` is the whole-job rate in 2000-edge equivalents:
         iterations/s x (total edges / 2000), so that it is commensurable with the N = 1 line; the raw
-        iterations/s of the 8000-edge graph is config.raw_iters_per_sec.  `extra.weak_scaling` is the second
-        figure: 2000 edges PER GPU (2000*N in total) on the same 256 keyframes.
+        iterations/s of the 8000-edge graph is config.raw_iters_per_sec.  With --full, `extra.weak_scaling` is
+        the second figure: 2000 edges PER GPU (2000*N in total) on the same 256 keyframes.
 
 Launching: with --gpus N > 1 and no WORLD_SIZE in the environment this process starts the N ranks itself
 (`python -m torch.distributed.run --nproc-per-node N` on 127.0.0.1, like the reference's `mp.spawn`, train.py:184-186)
@@ -58,14 +67,22 @@ def parse():
     ap.add_argument("--edges-total", type=int, default=0, help="0 = 2000 for one GPU, 8000 (BASELINE configs[3]) otherwise")
     ap.add_argument("--edges-per-gpu", type=int, default=2000, help="weak-scaling second figure (N > 1)")
     ap.add_argument("--keyframes", type=int, default=256)
-    ap.add_argument("--no-extra", action="store_true", help="skip the other configs / the weak-scaling figure")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-corr", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the stage profile, the iterations=2 call shape, the other configs / the weak-scaling figure, "
+                         "the correlation operators, the CPU baselines and the rooflines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state after the last timed step as DIR/poses.npy and DIR/disps.npy (float32)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other configs / the weak-scaling figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-corr", action="store_true", help="with --full: skip the correlation operators")
     ap.add_argument("--corr-edges", type=int, default=256, help="edges per corr-lookup batch")
     ap.add_argument("--stub-backend", action="store_true",
                     help="plumbing test without a GPU (tests/test_bench_launch.py): CPU tensors, gloo, a compute backend "
                          "that only exercises the phase order and the collective; the line is marked invalid")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class _StubBackend:
@@ -120,9 +137,24 @@ def to_dev(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
+def dump_outputs(out_dir, solver, p, ranges, rank, world):
+    """The state the timed `ba` call hands back to its caller: poses (replicated on every rank) and the depth maps,
+    gathered from their owners.  Collective when world > 1; rank 0 writes."""
+    poses = p.poses.detach().clone()
+    disps = p.disps.detach().clone()
+    if world > 1:
+        solver.gather_disps(disps, ranges)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, t in (("poses", poses), ("disps", disps)):
+            np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+        log(f"outputs of the last timed step written to {out_dir}")
+
+
 def bench_ba(args, rank, world, dev, N, E, H=48, W=64, stereo=False, lm=1e-5, ep=1e-2, seed=2, steps=None,
-             profile=True):
-    """`steps` Gauss-Newton iterations of one `ba` call on an N-keyframe / E-edge graph (E = total over ranks)."""
+             profile=True, dump=None):
+    """`steps` Gauss-Newton iterations of one `ba` call on an N-keyframe / E-edge graph (E = total over ranks).
+    `dump`: a directory for the state after the timed call (dump_outputs)."""
     import torch.distributed as dist
     from droid_backends import ba_driver, synth
 
@@ -168,6 +200,8 @@ def bench_ba(args, rank, world, dev, N, E, H=48, W=64, stereo=False, lm=1e-5, ep
     st, m = solver.backend.status()
     if st & 11:
         raise RuntimeError(f"BA reported contract violation status={st}")
+    if dump:
+        dump_outputs(dump, solver, p, ranges, rank, world)
 
     info = dict(N=N, E=E, E_local=int(p.ii.shape[0]), M_local=int(p.eta.shape[0]), HW=H * W, P=prob.t1 - prob.t0,
                 chol_failed=bool(st & 4), steps=steps)
@@ -446,6 +480,74 @@ def cpu_model():
     return "unknown"
 
 
+def rooflines(info, stages, prob):
+    """--full: the four stage kernels of one iteration against their rooflines (durations from the stage
+    profile) and the one of the dominant stage."""
+    # ---- rooflines.  Durations: HIP events on the launch stream (stage_ms).  Algorithmic work:
+    # SURVEY.md section 8d.  `traffic`: FETCH_SIZE(x2, gfx950 wide-stream correction)+WRITE_SIZE per
+    # launch from the committed rocprofv3 --pmc passes of this same command (profiles/).
+    HW, E_l, M_l, Nk, P = info["HW"], info["E_local"], info["M_local"], info["N"], info["P"]
+    n = 6 * P
+    pmc, pmc_src = {}, None
+    for name in ("r03_pmc_summary.json", "r02_pmc_summary.json", "r01_pmc_summary.json"):
+        try:
+            pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+            pmc_src = "profiles/" + name
+            break
+        except Exception:
+            continue
+
+    def traffic(kernel):
+        k = pmc.get(kernel) or pmc.get(kernel.replace("<false>", ""))   # (r01 / r02 summaries: not yet a template)
+        if not k or "FETCH_SIZE" not in k or "WRITE_SIZE" not in k:
+            return None
+        return (2.0 * k["FETCH_SIZE"]["mean"] + k["WRITE_SIZE"]["mean"]) * 1024.0
+
+    # NOT measured in this run: PMC counters need their own rocprofv3 passes (tools/collect_profiles.sh)
+    tsrc = (pmc_src + " (rocprofv3 --pmc passes of this command at the commit that wrote the file; "
+                      "FETCH_SIZE x2 per the gfx950 128-byte-request correction, calibrated in "
+                      "profiles/r02_gather16_calibration.txt)") if pmc_src else None
+
+    def hbm(kernel, stage, alg_bytes, note):
+        a = alg_bytes / (stages[stage] * 1e-3) / 1e9
+        return dict(kernel=kernel, bound="hbm", achieved=a, peak=HBM_PEAK_GBS, unit="GB/s",
+                    frac=a / HBM_PEAK_GBS, traffic=traffic(kernel), traffic_source=tsrc, algorithmic_bytes=alg_bytes, note=note)
+
+    def flop(kernel, stage, flops, peak, note):
+        a = flops / (stages[stage] * 1e-3) / 1e12
+        return dict(kernel=kernel, bound="mfma", achieved=a, peak=peak, unit="TFLOP/s", frac=a / peak,
+                    traffic=traffic(kernel), traffic_source=tsrc, algorithmic_flops=flops, note=note)
+
+    deg = np.bincount(prob.ii, minlength=Nk)  # Schur GEMM, symmetric minimum (SURVEY.md section 8d)
+    nk = deg + 1
+    schur_flops = float(np.sum((6 * nk) * (6 * nk + 1) * HW + 6 * nk * HW)) * (E_l / max(1, len(prob.ii)))
+    # kernel names as the library dispatches them (ba_internal.hpp::ba_carve): dense graphs (mean out-degree >= 12) run
+    # the linearisation that writes the E rows and the bf16x3 SYRK; few depth slots split a slot's edges over workgroups
+    wide = M_l > 0 and E_l >= 12 * M_l and HW % 32 == 0
+    zsplit = M_l > 0 and 1536 // (M_l * ((HW + 511) // 512)) > 1
+    lin_name = "droid::ba_lin_kernel<true, %s, %s>" % ("true" if wide else "false", "true" if zsplit else "false")
+    schur_name = "droid::ba_syrk3_kernel<256, 12, 1, 1, true, true>" if wide else "droid::ba_schur2_kernel"
+    schur_note = ("dense-slot Schur SYRK (+ class-2 launch + fold kernel, in the stage time): symmetric-minimum fp32-equivalent flops "
+                  "against the fp32 MFMA peak; executed as six v_mfma_f32_16x16x32_bf16 per 32-deep step on three-way split "
+                  "operands (DESIGN.md section 7)") if wide else (
+                  "Schur SYRK (+ per-slot fold kernel, in the stage time), symmetric-minimum flops, fp32 MFMA peak; the kernel "
+                  "also recomputes the E rows; fp32 MFMA and VALU time add up on gfx950 (tools/micro/mfma_valu_overlap.hip)")
+    kernels = [
+        flop("droid::chol_factor_persistent_kernel<false>", "factor", n ** 3 / 3.0, FP64_VEC_PEAK_TFLOPS,
+             "fp64 Cholesky of the (6P)^2 reduced camera system in one launch, n^3/3 flops over ceil(n/64) "
+             "dependent block columns: a pivot-latency chain, priced against the fp64 vector/MFMA peak"),
+        hbm(lin_name, "linearize", 16.0 * E_l * HW + 16.0 * M_l * HW + 56.0 * Nk,
+            "compulsory bytes of one BA iteration (16*E*HW + 16*M*HW + 56*N)"),
+        flop(schur_name, "schur", schur_flops, 157.3, schur_note),
+        hbm("droid::ba_backsub_kernel", "update", 8.0 * E_l * HW + 16.0 * M_l * HW,
+            "weights (8*E*HW) + Q, w, disps r/w (16*M*HW)"),
+    ]
+    dom = max((k for k in stages if k not in ("total", "unused")), key=lambda k: stages[k])
+    stage_of = {"factor": 0, "linearize": 1, "schur": 2, "update": 3}
+    roof = dict(kernels[stage_of.get(dom, 0)])
+    return roof, kernels
+
+
 def main_stub(args, rank, world):
     """--stub-backend: the launch / rendezvous / collective plumbing of a multi-rank run on CPU (gloo)."""
     import torch.distributed as dist
@@ -454,10 +556,11 @@ def main_stub(args, rank, world):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("gloo")
     dt, _, info, _ = bench_ba(args, rank, world, dev, args.keyframes, args.edges_total or 32, H=8, W=8, steps=args.steps,
-                              profile=False)
+                              profile=False, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps({"metric": "BA update iters/sec (STUB BACKEND: plumbing only, not a measurement)", "value": None,
                           "valid": False, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                          "ms_per_step": dt / args.steps * 1e3,
                           "config": {"workload": "stub", "edges_total": info["E"], "edges_local_rank0": info["E_local"],
                                      "stub_allreduce_sum": info.get("stub_allreduce_sum")}}), flush=True)
     if world > 1:
@@ -497,9 +600,10 @@ def main():
     from droid_backends import synth
     E_total = args.edges_total if args.edges_total > 0 else (2000 if world == 1 else 8000)
     seed = synth.CONFIG_SEEDS["cfg3"] if E_total == 2000 else synth.CONFIG_SEEDS["cfg4"]
-    dt, stages, info, prob = bench_ba(args, rank, world, dev, args.keyframes, E_total, seed=seed)
+    dt, stages, info, prob = bench_ba(args, rank, world, dev, args.keyframes, E_total, seed=seed, profile=args.full,
+                                      dump=args.dump_outputs)
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1:
             # the other BASELINE configs on this GPU (parity of each: tests/test_gpu_ba*.py, test_gpu_baseline_shapes.py)
             cfgs = {}
@@ -522,7 +626,7 @@ def main():
                                          ms_per_step=dw / args.steps * 1e3, scaling="weak")
             torch.cuda.empty_cache()
     corr = None
-    if not args.no_corr:
+    if args.full and not args.no_corr:
         try:
             corr = bench_corr(args, rank, world, dev, prob)
         except torch.OutOfMemoryError as e:  # pragma: no cover
@@ -543,93 +647,31 @@ def main():
         K = args.steps
         raw = K / dt
         value = raw * (info["E"] / 2000.0)
-        # ---- rooflines.  Durations: HIP events on the launch stream (stage_ms).  Algorithmic work:
-        # SURVEY.md section 8d.  `traffic`: FETCH_SIZE(x2, gfx950 wide-stream correction)+WRITE_SIZE per
-        # launch from the committed rocprofv3 --pmc passes of this same command (profiles/).
-        HW, E_l, M_l, Nk, P = info["HW"], info["E_local"], info["M_local"], info["N"], info["P"]
-        n = 6 * P
-        pmc, pmc_src = {}, None
-        for name in ("r03_pmc_summary.json", "r02_pmc_summary.json", "r01_pmc_summary.json"):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-                pmc_src = "profiles/" + name
-                break
-            except Exception:
-                continue
-
-        def traffic(kernel):
-            k = pmc.get(kernel) or pmc.get(kernel.replace("<false>", ""))   # (r01 / r02 summaries: not yet a template)
-            if not k or "FETCH_SIZE" not in k or "WRITE_SIZE" not in k:
-                return None
-            return (2.0 * k["FETCH_SIZE"]["mean"] + k["WRITE_SIZE"]["mean"]) * 1024.0
-
-        # NOT measured in this run: PMC counters need their own rocprofv3 passes (tools/collect_profiles.sh)
-        tsrc = (pmc_src + " (rocprofv3 --pmc passes of this command at the commit that wrote the file; "
-                          "FETCH_SIZE x2 per the gfx950 128-byte-request correction, calibrated in "
-                          "profiles/r02_gather16_calibration.txt)") if pmc_src else None
-
-        def hbm(kernel, stage, alg_bytes, note):
-            a = alg_bytes / (stages[stage] * 1e-3) / 1e9
-            return dict(kernel=kernel, bound="hbm", achieved=a, peak=HBM_PEAK_GBS, unit="GB/s",
-                        frac=a / HBM_PEAK_GBS, traffic=traffic(kernel), traffic_source=tsrc, algorithmic_bytes=alg_bytes, note=note)
-
-        def flop(kernel, stage, flops, peak, note):
-            a = flops / (stages[stage] * 1e-3) / 1e12
-            return dict(kernel=kernel, bound="mfma", achieved=a, peak=peak, unit="TFLOP/s", frac=a / peak,
-                        traffic=traffic(kernel), traffic_source=tsrc, algorithmic_flops=flops, note=note)
-
-        deg = np.bincount(prob.ii, minlength=Nk)  # Schur GEMM, symmetric minimum
-        nk = deg + 1
-        schur_flops = float(np.sum((6 * nk) * (6 * nk + 1) * HW + 6 * nk * HW)) * (E_l / max(1, len(prob.ii)))
-        # kernel names as the library dispatches them (ba_internal.hpp::ba_carve): dense graphs (mean out-degree >= 12) run
-        # the linearisation that writes the E rows and the bf16x3 SYRK; few depth slots split a slot's edges over workgroups
-        wide = M_l > 0 and E_l >= 12 * M_l and HW % 32 == 0
-        zsplit = M_l > 0 and 1536 // (M_l * ((HW + 511) // 512)) > 1
-        lin_name = "droid::ba_lin_kernel<true, %s, %s>" % ("true" if wide else "false", "true" if zsplit else "false")
-        schur_name = "droid::ba_syrk3_kernel<256, 12, 1, 1, true, true>" if wide else "droid::ba_schur2_kernel"
-        schur_note = ("dense-slot Schur SYRK (+ class-2 launch + fold kernel, in the stage time): symmetric-minimum fp32-equivalent flops "
-                      "against the fp32 MFMA peak; executed as six v_mfma_f32_16x16x32_bf16 per 32-deep step on three-way split "
-                      "operands (DESIGN.md section 7)") if wide else (
-                      "Schur SYRK (+ per-slot fold kernel, in the stage time), symmetric-minimum flops, fp32 MFMA peak; the kernel "
-                      "also recomputes the E rows; fp32 MFMA and VALU time add up on gfx950 (tools/micro/mfma_valu_overlap.hip)")
-        kernels = [
-            flop("droid::chol_factor_persistent_kernel<false>", "factor", n ** 3 / 3.0, FP64_VEC_PEAK_TFLOPS,
-                 "fp64 Cholesky of the (6P)^2 reduced camera system in one launch, n^3/3 flops over ceil(n/64) "
-                 "dependent block columns: a pivot-latency chain, priced against the fp64 vector/MFMA peak"),
-            hbm(lin_name, "linearize", 16.0 * E_l * HW + 16.0 * M_l * HW + 56.0 * Nk,
-                "compulsory bytes of one BA iteration (16*E*HW + 16*M*HW + 56*N)"),
-            flop(schur_name, "schur", schur_flops, 157.3, schur_note),
-            hbm("droid::ba_backsub_kernel", "update", 8.0 * E_l * HW + 16.0 * M_l * HW,
-                "weights (8*E*HW) + Q, w, disps r/w (16*M*HW)"),
-        ]
-        dom = max((k for k in stages if k not in ("total", "unused")), key=lambda k: stages[k])
-        stage_of = {"factor": 0, "linearize": 1, "schur": 2, "update": 3}
-        roof = dict(kernels[stage_of.get(dom, 0)])
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            try:
-                cpu = cpu_baseline()
-            except Exception as e:  # pragma: no cover
-                log("cpu baseline failed:", e)
+        config = {"workload": f"{info['N']}-keyframe / {info['E']}-edge global BA, 48x64, t0=1, lm=1e-5 ep=1e-2"
+                              + (" (BASELINE configs[2])" if (world == 1 and info["E"] == 2000) else
+                                 (" (BASELINE configs[3])" if info["E"] == 8000 else "")
+                                 + (f", edges sharded by source frame over {world} GPUs, 1 all-reduce/iter" if world > 1 else "")),
+                  "raw_iters_per_sec": raw, "edges_total": info["E"], "edges_per_gpu": info["E"] / world}
+        if args.full:
+            config.update(ms_per_call_iterations2=info["call2_ms"], stage_ms=stages)
+        config.update(solve="fp64 dense Cholesky on device", chol_failed=info["chol_failed"])
         line = {
             "metric": "BA update iters/sec (2000-edge equivalents; 256 keyframes, 48x64)",
             "value": value, "unit": "iters/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
             "ms_per_step": dt / K * 1e3, "higher_is_better": True, "scaling": "weak" if world == 1 else "strong",
             "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{info['N']}-keyframe / {info['E']}-edge global BA, 48x64, t0=1, lm=1e-5 ep=1e-2"
-                                   + (" (BASELINE configs[2])" if (world == 1 and info["E"] == 2000) else
-                                      (" (BASELINE configs[3])" if info["E"] == 8000 else "")
-                                      + (f", edges sharded by source frame over {world} GPUs, 1 all-reduce/iter" if world > 1 else "")),
-                       "raw_iters_per_sec": raw, "edges_total": info["E"], "edges_per_gpu": info["E"] / world,
-                       "ms_per_call_iterations2": info["call2_ms"], "stage_ms": stages,
-                       "solve": "fp64 dense Cholesky on device", "chol_failed": info["chol_failed"]},
-            "roofline": roof,
-            "rooflines": kernels,
-            "cpu_baseline": cpu,
-            "corr": corr,
-            "extra": extra,
+            "config": config,
         }
+        if args.full:
+            roof, kernels = rooflines(info, stages, prob)
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:
+                try:
+                    cpu = cpu_baseline()
+                except Exception as e:  # pragma: no cover
+                    log("cpu baseline failed:", e)
+            line.update(roofline=roof, rooflines=kernels, cpu_baseline=cpu, corr=corr, extra=extra)
         print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -8,6 +8,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ["--no-corr", "--no-cpu-baseline", "--no-extra", "--stub-backend", "--keyframes", "8", "--edges-total", "32",
           "--steps", "2", "--warmup", "1"]
@@ -48,3 +51,22 @@ def test_world_size_mismatch_is_an_error():
     assert r.returncode != 0
     assert "WORLD_SIZE=1" in r.stderr and "--gpus 2" in r.stderr
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_dump_outputs_writes_the_state_after_the_timed_steps(tmp_path, gpus):
+    """--dump-outputs DIR: rank 0 writes poses / disps (every rank's frames gathered) as float32 .npy, and the line
+    carries ms_per_step.  The stub backend does no arithmetic, so the state is the seeded input itself."""
+    from droid_backends import synth
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus)] + COMMON
+                       + ["--dump-outputs", str(out)], env=_env(), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["disps.npy", "poses.npy"]
+    p = synth.make_ba_problem(N=8, E=32, H=8, W=8, seed=2)
+    for name, want in (("poses", p.poses), ("disps", p.disps)):
+        got = np.load(out / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == want.shape, (name, got.dtype, got.shape)
+        assert np.array_equal(got, want.astype(np.float32)), name

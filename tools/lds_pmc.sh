@@ -2,8 +2,9 @@
 set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_BUSY_CYCLES -d $R/gpurun_out/ldspmc -- python3 $R/bench.py --no-extra --no-cpu-baseline --no-corr > /dev/null 2>&1 || echo "pass failed"
-f=$(ls -t $R/gpurun_out/ldspmc/*/*counter_collection.csv | head -1)
+O=${PROF_OUT:-$R/prof_out}
+rocprofv3 --kernel-trace --output-format csv --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_BUSY_CYCLES -d $O/ldspmc -- python3 $R/bench.py --full --no-extra --no-cpu-baseline --no-corr > /dev/null 2>&1 || echo "pass failed"
+f=$(ls -t $O/ldspmc/*/*counter_collection.csv | head -1)
 python3 - "$f" <<'PY'
 import csv, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -3,9 +3,11 @@ set -e
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 T=${1:-run}
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$T -- python3 $R/bench.py --no-extra --no-cpu-baseline --no-corr > $R/gpurun_out/prof_$T.json 2> $R/gpurun_out/prof_$T.err
-f=$(ls $R/gpurun_out/prof_$T/*/*kernel_stats.csv | tail -1)
-cp $f $R/gpurun_out/prof_${T}_kernel_stats.csv
+O=${PROF_OUT:-$R/prof_out}
+mkdir -p $O
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 $R/bench.py --full --no-extra --no-cpu-baseline --no-corr > $O/prof_$T.json 2> $O/prof_$T.err
+f=$(ls $O/prof_$T/*/*kernel_stats.csv | tail -1)
+cp $f $O/prof_${T}_kernel_stats.csv
 python3 - "$f" <<'PY'
 import csv,sys
 rows=list(csv.DictReader(open(sys.argv[1])))
