@@ -57,14 +57,19 @@ static thread_local char g_err[512] = "";
 // workspace -> host-visible status words (droid_ba_attach_status_mirror)
 static std::map<const void*, int*> g_mirror;
 static std::mutex g_mirror_mu;
-// workspace -> launch hints (droid_ba_attach_launch_hints) + tag of the last prepare
+// workspace -> launch hints (droid_ba_attach_launch_hints) + tag of the last prepare.  Tags come from ONE counter of the
+// process that attaching never resets: the words a prepare reads back may still hold the hint of an earlier prepare (of
+// this buffer, or of another one the same words were attached to before: a grown workspace), possibly still in flight,
+// and that hint must never carry the current tag.
 struct HintState { int* ptr; int tag; };
 static std::map<const void*, HintState> g_hint;
+static int g_hint_tag = 0;   // guarded by g_mirror_mu
 static void hints_of(BaView& v, const void* ws, bool new_call) {
   std::lock_guard<std::mutex> lock(g_mirror_mu);
   auto it = g_hint.find(ws);
   if (it == g_hint.end()) return;
-  if (new_call) it->second.tag = it->second.tag >= (1 << 30) ? 1 : it->second.tag + 1;
+  if (new_call) it->second.tag = g_hint_tag = g_hint_tag >= (1 << 30) ? 1 : g_hint_tag + 1;
+  if (it->second.tag == 0) return;   // no prepare since the words were attached: nothing to expect in them
   v.hint = it->second.ptr;
   v.hint_tag = it->second.tag;
 }
@@ -463,7 +468,10 @@ int droid_ba_status(const void* workspace, void* stream, int* status_out, int* d
 int droid_ba_attach_launch_hints(const void* workspace, int* hints) {
   if (!workspace) return fail(DROID_E_ARG, "ba_attach_launch_hints: null %s", "workspace");
   std::lock_guard<std::mutex> lock(g_mirror_mu);
-  if (hints) g_hint[workspace] = HintState{hints, 0};
+  if (hints) {
+    hints[0] = hints[1] = 0;   // tag 0 is never a prepare's
+    g_hint[workspace] = HintState{hints, 0};
+  }
   else g_hint.erase(workspace);
   return DROID_OK;
 }

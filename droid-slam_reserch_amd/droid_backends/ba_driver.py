@@ -65,6 +65,9 @@ class HipBackend:
     def __init__(self):
         self.lib = _lib.load()
         self.ws = None
+        # include/droid_backends_hip.h: launch hints.  One pair of words for the life of the backend: a prepare that is
+        # still queued when the workspace grows writes into them later, so they must outlive every workspace
+        self.hints = torch.zeros(2, dtype=torch.int32).pin_memory()
 
     def __del__(self):
         # the library keys the launch hints by workspace address: drop the registration with the buffers it points to
@@ -89,7 +92,6 @@ class HipBackend:
             if self.ws is not None:
                 self.lib.droid_ba_attach_launch_hints(self.ws.data_ptr(), None)
             self.ws = torch.empty(nbytes + 4096, dtype=torch.uint8, device=p.poses.device)
-            self.hints = torch.zeros(2, dtype=torch.int32).pin_memory()   # include/droid_backends_hip.h: launch hints
             _lib.check(self.lib.droid_ba_attach_launch_hints(self.ws.data_ptr(), self.hints.data_ptr()), "ba (launch hints)")
         self._dims = (E, nbuf, H, W, M, t0, t1)
         s = torch.cuda.current_stream().cuda_stream

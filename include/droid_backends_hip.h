@@ -226,7 +226,8 @@ int droid_ba_status(const void *workspace, void *stream, int *status_out, int *d
  * workspaces (droid_backends keeps one per (device, stream)). */
 int droid_ba_attach_status_mirror(const void *workspace, int *mirror);
 
-/* Launch hints (optional): `hints` points to 2 ZEROED ints of page-locked host memory that the device can address.
+/* Launch hints (optional): `hints` points to 2 ints of page-locked host memory that the device can address (attaching
+ * zeroes them; tags are unique in the process, so a late hint of an earlier prepare is never taken for the current one).
  * droid_ba_prepare's kernel then writes {tag of that prepare, number of depth slots of Schur class 3 (more edges than the
  * regular Schur kernels take: block pairs)} there, and droid_ba_build / droid_ba leave the block-pair launch of an
  * iteration out when the hint of the CURRENT prepare has arrived and says "none" (most graphs: 5 us per iteration).

@@ -1,0 +1,96 @@
+"""CPU tests of the checker of tests/test_gpu_ba_stages.py (no GPU): the scaled entry-wise metric and the dense graphs' bar
+pass the oracle's own fp32 restatement and fail a system with one block of S off by 1e-5 relative or one write into a block
+that must stay zero; the header words the harness reads are the ones csrc/ba_internal.hpp defines; the graph table
+covers every Schur kernel class."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import util
+from stage_graphs import GRAPHS
+from util import STAGE_BARS, ba_args, scaled_system_errors
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_word_indices_match_ba_internal():
+    src = open(os.path.join(ROOT, "droid-slam_reserch_amd", "csrc", "ba_internal.hpp")).read()
+    m = re.search(r"enum\s*\{\s*(HDR_STATUS[^}]*)\}", src)
+    assert m, "enum HDR_* not found"
+    body = re.sub(r"//[^\n]*", "", m.group(1))
+    words = {k: int(v) for k, v in re.findall(r"(HDR_\w+)\s*=\s*(\d+)", body)}
+    for name in ("HDR_M", "HDR_NC1", "HDR_NC2"):
+        assert getattr(util, name) == words[name], (name, getattr(util, name), words[name])
+
+
+def test_stage_graphs_cover_every_schur_class():
+    assert set().union(*(c for _, _, c in GRAPHS.values())) == {0, 1, 2, 3, "motion"}
+    assert {f for _, f, _ in GRAPHS.values()} <= set(STAGE_BARS)
+
+
+@pytest.fixture(scope="module")
+def synth():
+    from droid_backends import synth
+    return synth
+
+
+# Dense graphs whose largest off-diagonal 6x6 block of S carries >= 0.18 of sqrt(H_aa H_bb): a 1e-5 error in it is >= 1.8e-6.
+# (The hub graphs are left out: the fp32 restatement's rhs, 100-edge sums in fp32, is 1.1-1.4e-6 off there -- above the bar
+# the device, which keeps fp64 totals, is held to.)
+@pytest.mark.parametrize("name", ["dense36_syrk", "dense20_few_stages", "variant_window_t0_3", "variant_rgbd",
+                                  "variant_stereo_pairs"])
+def test_checker_passes_fp32_and_fails_a_wrong_block(oracle, synth, name):
+    build, family, _ = GRAPHS[name]
+    assert family == "dense"
+    bars = STAGE_BARS[family]
+    p = build(synth)
+    r64 = oracle.ba(*ba_args(p), 1, p.lm, p.ep, False, debug=True)
+    r32 = oracle.ba(*ba_args(p), 1, p.lm, p.ep, False, debug=True, precision="f32")
+    Ho, bo = r64["H"], r64["b"]
+    e = scaled_system_errors(r32["H"], r32["b"], Ho, bo)
+    print(f"[{name}] fp32 oracle: H {e['H']:.2e} b {e['b']:.2e}, {e['zero_blocks']} zero blocks")
+    util.assert_system_close(e, bars, name)
+
+    # the off-diagonal block that is largest against its diagonal, scaled by 1 + 1e-5
+    n = Ho.shape[0]
+    P = n // 6
+    s = 1.0 / np.sqrt(np.diag(Ho))
+    blk = (np.abs(np.tril(Ho)) * s[:, None] * s[None, :]).reshape(P, 6, P, 6).max(axis=(1, 3))
+    blk[np.triu_indices(P)] = 0
+    a, b = np.unravel_index(np.argmax(blk), blk.shape)
+    assert blk[a, b] >= 0.18, blk[a, b]
+    bad = r32["H"].copy()
+    bad[6 * a:6 * a + 6, 6 * b:6 * b + 6] *= 1 + 1e-5
+    e = scaled_system_errors(bad, r32["b"], Ho, bo)
+    assert e["H"] >= bars["H"], (name, e["H"], bars["H"])
+    with pytest.raises(AssertionError):
+        util.assert_system_close(e, bars, name)
+
+    # one tiny value in a block that is exactly zero in the oracle (the graphs with a window border have such blocks)
+    bad = r32["H"].copy()
+    zero = np.argwhere(np.tril((Ho.reshape(P, 6, P, 6) == 0).all(axis=(1, 3)), -1))
+    if len(zero):
+        a, b = zero[len(zero) // 2]
+        bad[6 * a + 3, 6 * b + 2] = 1e-12 * np.sqrt(Ho[6 * a + 3, 6 * a + 3] * Ho[6 * b + 2, 6 * b + 2])
+        e = scaled_system_errors(bad, r32["b"], Ho, bo)
+        assert e["stray"] == 1 and e["H"] < bars["H"], e
+        with pytest.raises(AssertionError):
+            util.assert_system_close(e, bars, name)
+
+
+def test_checker_rejects_a_nonzero_row_of_a_dead_pose(oracle, synth):
+    """A pose without observations has a zero row in the oracle's system: the device's must be exactly zero too."""
+    p = GRAPHS["cfg1"][0](synth)
+    r = oracle.ba(*ba_args(p), 1, p.lm, p.ep, False, debug=True)
+    H, b = r["H"].copy(), r["b"].copy()
+    n = H.shape[0] + 6
+    Ho = np.zeros((n, n))
+    Ho[:-6, :-6] = H
+    bo = np.concatenate([b, np.zeros(6)])
+    Hd = Ho.copy()
+    assert scaled_system_errors(Hd, bo, Ho, bo)["dead"] == 0
+    Hd[n - 2, 3] = 1e-30
+    e = scaled_system_errors(Hd, bo, Ho, bo)
+    assert e["dead"] == 1 and e["H"] == 0.0

@@ -116,3 +116,156 @@ def assert_composite_parity(hip, ref, tol, tag="", sensitive=None, hard=2e-3):
     assert mask.sum() <= 2e-4 * mask.size, (tag, int(mask.sum()))   # the set stays tiny
     assert stray == 0 and d.max() < hard, (tag, n_out, stray, float(d.max()))
     return et, er, ed, n_out
+
+
+# ---- stage-by-stage parity of one Gauss-Newton iteration (tests/test_gpu_ba_stages.py) ------------------------------
+# Words of the workspace header (csrc/ba_internal.hpp: enum HDR_*, the first thing ba_carve places in the workspace):
+# depth slots, and the slots served by the two SYRK instances (Schur classes 1 and 2).  tests/test_stage_checker.py
+# parses the enum so that these stay equal to it.
+HDR_M, HDR_NC1, HDR_NC2 = 1, 5, 6
+
+# Bars per graph family (tests/stage_graphs.py), set from the errors measured on the MI355X (DESIGN.md section 5,
+# "stage by stage"), at most 4x the worst of them:
+#   H   max |dH_ab| / sqrt(H_aa H_bb) of the lower triangle, (H_aa: the oracle's fp64 diagonal)
+#   b   max |db_a| / sqrt(H_aa), relative to max |b_a| / sqrt(H_aa)
+#   dx  max |dx - dx64| / max |dx64|, dx64 = fp64 solve of the device's own damped system
+#   state  max over |dt|, rotation angle, |ddisp| against the oracle's back-substitution and retraction of the
+#          device's own system
+STAGE_BARS = {
+    "sparse": dict(H=5.0e-7, b=4.4e-7, dx=1.6e-7, state=2.2e-5),
+    "wide": dict(H=4.1e-7, b=2.2e-7, dx=1.3e-7, state=1.3e-5),
+    "stereo": dict(H=4.8e-7, b=1.9e-7, dx=1.6e-7, state=7.3e-6),
+    "dense": dict(H=5.4e-7, b=3.8e-7, dx=1.5e-7, state=2.7e-6),
+    "motion": dict(H=3.4e-7, b=1.3e-7, dx=1.1e-7, state=1.1e-7),
+}
+PACKED_BAR = 1e-12   # build_packed + unpack vs build: the same sums in another order of the fp64 atomics
+
+
+def scaled_system_errors(Hd, bd, Ho, bo):
+    """Entry-wise distance of a reduced system (Hd, bd) from the reference (Ho, bo), lower triangles.  The Schur
+    complement is PSD, so |H_ab| <= sqrt(H_aa H_bb): scaling by the reference's diagonal bounds every entry by 1 and
+    separates a wrong kernel from fp32 noise in the well AND the weakly observed parts of the graph.  Rows whose reference
+    diagonal is 0 must be exactly 0 (counted in `dead`), and so must every 6x6 block that is exactly 0 in the reference
+    (`stray`: a write into the wrong slot)."""
+    n = Ho.shape[0]
+    Ho, Hd = np.tril(Ho), np.tril(Hd[:n, :n])
+    dg = np.diag(Ho).copy()
+    live = dg > 0
+    si = np.where(live, 1.0 / np.sqrt(np.where(live, dg, 1.0)), 0.0)
+    dead = int(np.count_nonzero(Hd[~live, :]) + np.count_nonzero(Hd[:, ~live]) + np.count_nonzero(bd[~live]))
+    eh = float((np.abs(Hd - Ho) * si[:, None] * si[None, :]).max()) if n else 0.0
+    P = n // 6
+    tri = np.tril(np.ones((P, P), bool))
+    zo = (Ho.reshape(P, 6, P, 6) == 0).all(axis=(1, 3)) & tri
+    zd = (Hd.reshape(P, 6, P, 6) == 0).all(axis=(1, 3))
+    bscale = max(float((np.abs(bo) * si).max()) if n else 0.0, 1e-300)
+    eb = float((np.abs(bd - bo) * si).max()) / bscale if n else 0.0
+    return dict(H=eh, b=eb, zero_blocks=int(zo.sum()), stray=int((zo & ~zd).sum()), dead=dead)
+
+
+def assert_system_close(err, bars, tag=""):
+    assert err["dead"] == 0 and err["stray"] == 0, (tag, err)
+    assert err["H"] < bars["H"] and err["b"] < bars["b"], (tag, err, bars)
+
+
+def damped_solve(H, b, lm, ep):
+    """fp64 solve of a reduced system the way droid_ba_solve_update damps it (oracle/ba_oracle_impl.h solve_system:
+    diag += ep + lm diag); lm, ep rounded to float32 like the C ABI's arguments.  H: lower triangle read."""
+    lm, ep = float(np.float32(lm)), float(np.float32(ep))
+    A = np.tril(H) + np.tril(H, -1).T
+    A[np.diag_indices_from(A)] += ep + lm * np.diag(A)
+    return np.linalg.solve(A, b)
+
+
+def run_ba_stages(backends, p, torch, motion_only=False, packed=False):
+    """One Gauss-Newton iteration through the phase ABI on a workspace of its own, with launch hints of its own:
+    droid_ba_prepare, droid_ba_build (its system copied before the solve factors it in place), optionally
+    droid_ba_build_packed + droid_ba_unpack_system (copied too), droid_ba_solve_update.  Returns the copies, the
+    state after the update, dx, the header words and the hint words {tag, slots of Schur class 3}."""
+    import ctypes
+    lib = backends._lib.load()
+    d = to_dev(p, torch)
+    nbuf, H, W = p.disps.shape
+    E, P = len(p.ii), p.t1 - p.t0
+    M = 0 if motion_only else p.eta.shape[0]
+    n = 6 * P
+    eta = None if motion_only else d["eta"].data_ptr()
+    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, M)
+    assert nbytes > 0
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    hints = torch.zeros(2, dtype=torch.int32).pin_memory()
+    dx = torch.zeros((P, 6), dtype=torch.float32, device="cuda")
+    dz = torch.zeros((max(M, 1), H * W), dtype=torch.float32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    args = (d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(), d["disps_sens"].data_ptr(),
+            d["targets"].data_ptr(), d["weights"].data_ptr(), eta, d["ii"].data_ptr(), d["jj"].data_ptr(),
+            E, nbuf, H, W, M, p.t0, p.t1, int(motion_only), ws.data_ptr(), nbytes, s)
+    nel = ctypes.c_size_t(0)
+    ptr = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, M, ctypes.byref(nel))
+    off = ptr - ws.data_ptr()
+    system = lambda: ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, -1)[:, :n].cpu().numpy().copy()
+    assert lib.droid_ba_attach_launch_hints(ws.data_ptr(), hints.data_ptr()) == 0
+    try:
+        assert lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, M, p.t0, p.t1, 0, nbuf,
+                                    int(motion_only), ws.data_ptr(), nbytes, s) == 0
+        assert lib.droid_ba_build(*args) == 0
+        torch.cuda.synchronize()
+        hdr = ws[:64].view(torch.int32).cpu().numpy().copy()
+        out = dict(system=system(), hdr=hdr, hint=(int(hints[0]), int(hints[1])))
+        if packed:
+            assert lib.droid_ba_build_packed(*args) == 0
+            assert lib.droid_ba_unpack_system(E, nbuf, H, W, M, p.t0, p.t1, int(motion_only), ws.data_ptr(), nbytes,
+                                              s) == 0
+            torch.cuda.synchronize()
+            out["system_packed"] = system()
+        assert lib.droid_ba_solve_update(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
+                                         d["weights"].data_ptr(), d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W,
+                                         M, p.t0, p.t1, float(p.lm), float(p.ep), int(motion_only), dx.data_ptr(),
+                                         dz.data_ptr() if M > 0 else None, ws.data_ptr(), nbytes, s) == 0
+        torch.cuda.synchronize()
+        st, m = ctypes.c_int(0), ctypes.c_int(0)
+        assert lib.droid_ba_status(ws.data_ptr(), s, ctypes.byref(st), ctypes.byref(m)) == 0
+    finally:
+        lib.droid_ba_attach_launch_hints(ws.data_ptr(), None)
+    out.update(status=st.value, M=m.value, dx=dx.cpu().numpy(), poses=d["poses"].cpu().numpy(),
+               disps=d["disps"].cpu().numpy())
+    return out
+
+
+def slot_classes(stages, motion_only=False):
+    """Schur classes the device served, from the header words and the hint words run_ba_stages read."""
+    hdr, (tag, n3) = stages["hdr"], stages["hint"]
+    if motion_only:
+        return {"motion"} if hdr[HDR_M] == 0 else {"slots?"}
+    assert tag != 0, "the launch hint of the prepare has not arrived after a synchronisation"
+    counts = (hdr[HDR_M] - hdr[HDR_NC1] - hdr[HDR_NC2] - n3, hdr[HDR_NC1], hdr[HDR_NC2], n3)
+    assert min(counts) >= 0, counts
+    return {c for c, k in enumerate(counts) if k > 0}
+
+
+def stage_errors(oracle, p, stages, motion_only=False):
+    """Errors of every stage of `stages` (run_ba_stages) against the oracle from the same inputs:
+    build (scaled entry-wise, zero blocks), packed build vs build, solve (dx vs an fp64 solve of the device's own
+    system) and back-substitution + retraction (the oracle's, applied to the device's own system)."""
+    nbuf = p.disps.shape[0]
+    ph = oracle.BAPhases()
+    Ho, bo = ph.build(*ba_args(p), 0, nbuf, motion_only)
+    sysd = stages["system"]
+    n = Ho.shape[0]
+    Hd, bd = sysd[:n], sysd[n]
+    err = scaled_system_errors(Hd, bd, Ho, bo)
+    if "system_packed" in stages:
+        sp = stages["system_packed"]
+        e = scaled_system_errors(sp[:n], sp[n], Hd, bd)
+        err["packed"] = max(e["H"], e["b"])
+        err["packed_stray"] = e["stray"] + e["dead"]
+    x = damped_solve(Hd, bd, p.lm, p.ep)
+    err["dx"] = float(np.abs(stages["dx"].reshape(-1) - x).max() / max(np.abs(x).max(), 1e-300))
+    lm, ep = float(np.float32(p.lm)), float(np.float32(p.ep))
+    poses, disps, _ = ph.finish(np.tril(Hd) + np.tril(Hd, -1).T, bd, lm, ep)
+    et = float(np.abs(stages["poses"][:, :3] - poses[:, :3]).max())
+    er = float(quat_angle(stages["poses"][:, 3:].astype(np.float64), poses[:, 3:]).max())
+    ed = float(np.abs(stages["disps"] - disps).max())
+    err["state"] = max(et, er, ed)
+    err["state_parts"] = (et, er, ed)
+    return err
