@@ -3,16 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace droid {
 
 constexpr int LIN_THREADS = 256;
-#ifdef LIN_PPT_AB
-constexpr int LIN_PPT = LIN_PPT_AB;              // A/B builds (tools/ab_test.sh)
-#else
 constexpr int LIN_PPT = 2;                       // pixels per thread per chunk
-#endif
 constexpr int LIN_CP = LIN_THREADS * LIN_PPT;    // pixels per workgroup chunk
 constexpr int CHOL_NB = 64;                      // Cholesky block size
 // row pitch of the augmented system in doubles: 128-byte rows, so 64-column tiles never share a cache line
@@ -118,9 +113,8 @@ struct BaSizes {
 };
 
 // Carves `ws` (may be null: size query only) into the view.  Host-only arithmetic.
-#ifndef SY_WGS
-#define SY_WGS 1024  // (slot, pixel range) workgroups of the class-1 SYRK launch: four per CU balance the uneven slots (A/B 512 / 768 / 1024 / 1536 / 2048: 270 / 265 / 253 / 262 / 270 us at 256 slots)
-#endif
+constexpr int SY_WGS = 1024;  // (slot, pixel range) workgroups of the class-1 SYRK launch: four per CU balance the uneven slots (A/B 512 / 768 / 1024 / 1536 / 2048: 270 / 265 / 253 / 262 / 270 us at 256 slots)
+constexpr int S2_WGS = 1536;  // (slot, pixel range) workgroups of the sparse Schur launch
 inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t0, int t1, int M) {
   v.E = E; v.nbuf = nbuf; v.H = H; v.W = W; v.HW = H * W;
   v.t0 = t0; v.t1 = t1; v.P = t1 - t0; v.M = M;
@@ -187,8 +181,7 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
   v.Gpart = nullptr;
   if (M > 0) {
     const int ptiles = (v.HW + 63) / 64;
-    static const int wg_target = getenv("DROID_S2_WGS") ? atoi(getenv("DROID_S2_WGS")) : 1536;  // diagnostics
-    int ns = wg_target / M;
+    int ns = S2_WGS / M;
     v.s2_split = ns < 1 ? 1 : (ns > ptiles ? ptiles : ns);
     size_t tiles = (size_t)E * 7 / 4 + (size_t)M + 1;
     if (tiles > (size_t)28 * M) tiles = (size_t)28 * M;

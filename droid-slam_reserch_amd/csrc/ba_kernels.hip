@@ -145,8 +145,8 @@ constexpr int SW_MID = 256;   // rows (incl. the w row) served by the two-workgr
 constexpr int SW_BIG = 512;   // rows served by the one-per-CU variant (85 entries)
 constexpr int SY_MAXSPLIT = 16;  // pixel ranges per slot of the SYRK kernels (each adds one fp64 atomic per output entry)
 
-// which kernel serves a slot: 0 = single 96-row block, 1/2 = SYRK-only kernel (E rows from v.Ebuf),
-// 3 = block pairs.
+// which kernel serves a slot: 0 = ba_schur2_kernel, 1/2 = SYRK-only kernel (E rows from v.Ebuf),
+// 3 = block pairs (ba_schur_fused_kernel).
 // `wide` is a host-side decision (mean out-degree of the graph): sparse graphs skip the two wide
 // launches altogether and leave their few dense slots to the block-pair kernel
 constexpr int S2_MAXE = 16;   // edges per slot served by ba_schur2_kernel (class 0)
@@ -811,13 +811,6 @@ __global__ __launch_bounds__(64) void ba_assemble_kernel(BaView v, const float* 
 // ------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifdef SCHUR_STAMPS
-__device__ unsigned long long g_schur_stamps[8 * 16];
-#define SSTAMP(i) do { if (stamp_on) { unsigned long long now_ = __builtin_amdgcn_s_memtime(); st_acc[i] += now_ - st_prev; st_prev = now_; } } while (0)
-#else
-#define SSTAMP(i) do { } while (0)
-#endif
-
 constexpr int SF_PITCH = SF_TP + 4;   // 16-byte aligned rows, conflict-free 16-byte MFMA operand reads
 constexpr int SF_MAXT = 11;           // max 16x16 output tiles per wave: ceil(7*6/4)
 
@@ -835,16 +828,13 @@ __device__ __forceinline__ void e_row(const Intr& K, const float* T, bool stereo
   for (int n = 0; n < 6; n++) eij[n] = su * L.Ju[n] + sv * L.Jv[n];  // dk:341, :374
 }
 
-// MULTI = false: slots of at most 16 entries (one row block; no second LDS block, so three
-// workgroups fit a CU and one's VALU staging overlaps another's MFMA phase); MULTI = true: the
-// rest.  Both variants are launched; a workgroup whose slot belongs to the other one exits.
-template <bool MULTI>
-__global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
+// Block-pair slots (class 3, see schur_class): a workgroup whose slot belongs to another class exits.
+__global__ __launch_bounds__(256, 2) void ba_schur_fused_kernel(
     BaView v, const float* __restrict__ poses, const float* __restrict__ disps,
     const float* __restrict__ intrinsics, const float* __restrict__ weights,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int wide) {
   __shared__ __attribute__((aligned(16))) float EA[(SF_RB + 16) * SF_PITCH];  // row block A (+ the w row, padded to a full tile)
-  __shared__ __attribute__((aligned(16))) float EB[MULTI ? SF_RB * SF_PITCH : 4];  // row block B (only for off-diagonal block pairs)
+  __shared__ __attribute__((aligned(16))) float EB[SF_RB * SF_PITCH];  // row block B (only for off-diagonal block pairs)
   __shared__ float SP[4 * 6 * SF_TP];            // partial self rows of the four edge subsets
   __shared__ SlotMeta sm;
   if ((int)blockIdx.x >= min(v.hdr[HDR_M], v.M)) return;
@@ -863,14 +853,10 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
   if (tile_beg >= tile_end) return;
   const bool has_self = (v.ent_row[e0] < v.M);  // the self row, when present, is entry 0
   const int nblk = (R + 1 + SF_RB - 1) / SF_RB;
-  if (schur_class(R + 1, v.seg_ptr[m + 1] - v.seg_ptr[m], wide) != (MULTI ? 3 : 0)) return;  // wide kernels serve 1, 2
+  if (schur_class(R + 1, v.seg_ptr[m + 1] - v.seg_ptr[m], wide) != 3) return;  // ba_schur2_kernel serves 0, the wide kernels 1, 2
   const int pixl = tid & (SF_TP - 1), part = tid >> 6;  // four threads per pixel split the edges
   const int x_beg = v.seg_ptr[m], nedges = v.seg_ptr[m + 1] - x_beg;
   const bool resident = nedges <= SLOT_MAXE;  // the usual case: metadata loaded once
-  // pose index of every Schur entry of the slot for the fold at the end (single-block variant: at most 16 entries):
-  // two dependent global loads per folded element made the fold 15 % of the workgroup's time
-  __shared__ int s_pose[MULTI ? 1 : 17];
-  if (!MULTI && tid < nent) s_pose[tid] = v.ent_pose[e0 + tid];
   if (resident) load_slot_meta(sm, v, poses, jj, f, x_beg, nedges, has_self ? 1 : 0);
   else __syncthreads();
 
@@ -894,11 +880,6 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
     }
   };
 
-#ifdef SCHUR_STAMPS
-  const bool stamp_on = (lane == 0) && (blockIdx.x == 100) && (blockIdx.y == 1);
-  unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long st_prev = __builtin_amdgcn_s_memtime();
-#endif
   for (int ba = 0; ba < nblk; ba++) {
     for (int bb = 0; bb <= ba; bb++) {
       const int ra0 = ba * SF_RB, rb0 = bb * SF_RB;
@@ -906,13 +887,12 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
       const int nb = min(SF_RB, R - rb0);                                  // rows of block B (E rows only)
       const int ta_n = (na + 15) / 16, tb_n = (nb + 15) / 16;
       const int ntiles = (ba == bb) ? ta_n * (ta_n + 1) / 2 : ta_n * tb_n;
-      constexpr int MAXT = MULTI ? SF_MAXT : 7;  // one block: at most 7*8/2 = 28 tiles over 4 waves
       // fp32 MFMA chains are kept to ONE 64-pixel tile (16 k-steps): the tile result is added to an fp64 total.
       // A chain over the whole pixel range (512 products) leaves 3e-7 of the block in every partial sum, which
       // the ill-conditioned reduced system (cond 1e6 on the 256-keyframe graph) turns into 3e-5 of pose error.
-      double tot[MAXT][4];
+      double tot[SF_MAXT][4];
 #pragma unroll
-      for (int t = 0; t < MAXT; t++)
+      for (int t = 0; t < SF_MAXT; t++)
 #pragma unroll
         for (int x = 0; x < 4; x++) tot[t][x] = 0.0;
 
@@ -924,9 +904,7 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
         float cur_w[2 * SF_PF];
 #pragma unroll
         for (int u = 0; u < 2 * SF_PF; u++) cur_w[u] = pf_w[u];
-        SSTAMP(0);
         __syncthreads();  // previous tile consumed
-        SSTAMP(1);
         // ---- stage: recompute the E rows of both blocks for 128 pixels
         {
           const float sq = sqrtf(cur_q);
@@ -990,7 +968,6 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
                 }
               }
             }
-            SSTAMP(2);
             if (self_here) {  // four partial sums per pixel, combined in a fixed order
 #pragma unroll
               for (int n = 0; n < 6; n++) SP[(part * 6 + n) * SF_TP + pixl] = selfacc[n];
@@ -1010,15 +987,13 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
             EA[(R - ra0) * SF_PITCH + pixl] = cur_wr * sq;
           }
         }
-        SSTAMP(3);
         __syncthreads();
-        SSTAMP(4);
         prefetch(tile + 1);
         // ---- SYRK of the tile: wave w owns output tiles w, w+4, ...
         const int r = lane & 15, g = lane >> 4;
         const float* Bs = (ba == bb) ? EA : EB;
 #pragma unroll
-        for (int t = 0; t < MAXT; t++) {
+        for (int t = 0; t < SF_MAXT; t++) {
           const int ti = wave + 4 * t;
           if (ti < ntiles) {
             int ta, tb;
@@ -1051,12 +1026,11 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
           }
         }
       }
-      SSTAMP(5);
       // ---- fold the accumulators into the dense system (A - S): lower triangle, fp64 atomics
       {
         const int r = lane & 15, g = lane >> 4;
 #pragma unroll
-        for (int t = 0; t < MAXT; t++) {
+        for (int t = 0; t < SF_MAXT; t++) {
           const int ti = wave + 4 * t;
           if (ti >= ntiles) continue;
           int ta, tb;
@@ -1078,12 +1052,12 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
             const int lj = rb0 + 16 * tb + r;          // B side, always an E row
             if (lj >= R || li > R) continue;
             const double val = -tot[t][x];
-            const int gj = 6 * (MULTI ? v.ent_pose[e0 + lj / 6] : s_pose[lj / 6]) + lj % 6;
+            const int gj = 6 * v.ent_pose[e0 + lj / 6] + lj % 6;
             if (li == R) {  // w row: reduced rhs
               atomicAdd(sys_at(v, v.n, gj), val);
               continue;
             }
-            const int gi = 6 * (MULTI ? v.ent_pose[e0 + li / 6] : s_pose[li / 6]) + li % 6;
+            const int gi = 6 * v.ent_pose[e0 + li / 6] + li % 6;
             const bool diag_tile = (ba == bb) && (ta == tb);
             if (diag_tile) {  // both (li,lj) and (lj,li) are computed
               if (gi >= gj) atomicAdd(sys_at(v, gi, gj), val);
@@ -1095,13 +1069,8 @@ __global__ __launch_bounds__(256, MULTI ? 2 : 3) void ba_schur_fused_kernel(
           }
         }
       }
-      SSTAMP(6);
     }
   }
-#ifdef SCHUR_STAMPS
-  if (stamp_on)
-    for (int i = 0; i < 8; i++) g_schur_stamps[wave * 8 + i] = st_acc[i];
-#endif
 }
 
 
@@ -1664,11 +1633,7 @@ __global__ __launch_bounds__(64 * NWV) void ba_syrk3_kernel(BaView v) {
 #pragma unroll
         for (int e = 0; e < 8; e++) x[e] = pf[k][it][e >> 2][e & 3] * sq[e];
         u32x4 p0, p1, p2;
-#ifdef SY3_NO_CONV
-        p0 = __builtin_bit_cast(u32x4, pf[k][it][0]); p1 = __builtin_bit_cast(u32x4, pf[k][it][1]); p2 = p0;
-#else
         split3_bf16(x, p0, p1, p2);
-#endif
         u32x4* P = PL + buf * 12 * NR + dst[it];
         P[0] = p0;
         P[4 * NR] = p1;
@@ -1728,9 +1693,6 @@ __global__ __launch_bounds__(64 * NWV) void ba_syrk3_kernel(BaView v) {
     t += c;
   };
   auto multiply = [&](int buf) {
-#ifdef SY3_NO_MM
-    return;
-#endif
     const u32x4* P = PL + buf * 12 * NR;
     auto frag = [&](int chunk) { return __builtin_bit_cast(bf16x8, P[chunk]); };
 #pragma unroll
@@ -1882,12 +1844,6 @@ __global__ __launch_bounds__(256) void ba_syrk_fold_kernel(BaView v, int wgs1, i
     }
   }
 }
-
-#ifdef SCHUR_STAMPS
-extern "C" int droid_debug_schur_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_schur_stamps), sizeof(unsigned long long) * 8 * 16);
-}
-#endif
 
 // ------------------------------------------------------------------------------------------
 // depth back-substitution + disparity retraction: dz = Q (w - sum_entries E^T dx), disps += dz
@@ -2160,7 +2116,7 @@ void launch_build_stage(const BaView& v, const float* poses, const float* disps,
           none3 = tag == v.hint_tag && __atomic_load_n(v.hint + 1, __ATOMIC_RELAXED) == 0;
         }
         if (!none3)
-          hipLaunchKernelGGL(ba_schur_fused_kernel<true>, dim3(v.M, nsplit), dim3(256), 0, s, v, poses, disps,
+          hipLaunchKernelGGL(ba_schur_fused_kernel, dim3(v.M, nsplit), dim3(256), 0, s, v, poses, disps,
                              intr, weights, ii, jj, wide);
         if (wide) {  // dense slots: SYRK straight from the E rows the linearisation wrote (v.Ebuf)
           hipLaunchKernelGGL((ba_syrk3_kernel<SW_MID, 12, 1, 1, true, true>), dim3(v.M, v.sy_ns[0], 1), dim3(768), 0, s, v);

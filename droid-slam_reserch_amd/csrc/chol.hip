@@ -182,18 +182,10 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 //   e = 1 - d y^2,  y <- y + y e (1/2 + 3/8 e)        (next term 5/16 e^3 ~ 4e-23)
 // = 5 instructions instead of the 8 of two Newton steps (-2.5 us per 1530-pivot factorisation, same residuals).
 __device__ __forceinline__ double rsqrt_nr(double d) {
-  double y = __builtin_amdgcn_rsq(d);
-#ifdef CHOL_TWO_NEWTON
-  double e = fma(-d * y, y, 1.0);
-  y = fma(0.5 * y, e, y);
-  e = fma(-d * y, y, 1.0);
-  y = fma(0.5 * y, e, y);
-#else
+  const double y = __builtin_amdgcn_rsq(d);
   const double e = fma(-d * y, y, 1.0);
   const double p = fma(0.375, e, 0.5);
-  y = fma(y * e, p, y);
-#endif
-  return y;
+  return fma(y * e, p, y);
 }
 
 // MFMA operand fetch from an LDS tile of pitch LDP.  `volatile` on purpose: left alone the compiler fuses neighbouring
@@ -210,32 +202,18 @@ __device__ __forceinline__ double lds_operand(const lds_f64* p) { return *(const
 // twice per workgroup; inlined, every call site is cold code and the instruction-cache misses cost
 // 4-5x the arithmetic (measured with s_memtime: 2.3-3.1k cycles cold vs 0.5k warm per call).
 template <bool ASSIGN>
-__device__ __forceinline__ void wave_gemm_nt16_inl(lds_f64* Cl, const lds_f64* Al, const lds_f64* Bl, int ldb) {
+__device__ __attribute__((noinline)) void wave_gemm_nt16(lds_f64* C, const lds_f64* A, const lds_f64* B, int ldb) {
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
-#ifdef CHOL_GEMM_FLAT
-  // (round 1 read the operands with FLAT loads: its ds_read form was 1.3 us slower per block column -- because the compiler
-  // had fused the reads into conflicting ds_read2_b64, see lds_operand() -- kept for A/B builds)
-  double* C = (double*)Cl;
-  const double* A = (const double*)Al;
-  const double* B = (const double*)Bl;
-  asm volatile("" : "+v"(C), "+v"(A), "+v"(B));
-#define DROID_GEMM_LD(p) (*(p))
-#else
-  lds_f64* C = Cl;
-  const lds_f64* A = Al;
-  const lds_f64* B = Bl;
-#define DROID_GEMM_LD(p) lds_operand(p)
-#endif
   f64x4 acc = {0.0, 0.0, 0.0, 0.0};
   double av[4], bv[4], cv[4];
 #ifdef CHOL_STAMPS
   if (ASSIGN && threadIdx.x == 0 && g_chol_lstamps[9] == 0) g_chol_lstamps[9] = wall_clock64();   // function entered
 #endif
 #pragma unroll
-  for (int k = 0; k < 4; k++) { av[k] = DROID_GEMM_LD(&A[r * LDP + 4 * k + g]); bv[k] = DROID_GEMM_LD(&B[r * ldb + 4 * k + g]); }
+  for (int k = 0; k < 4; k++) { av[k] = lds_operand(&A[r * LDP + 4 * k + g]); bv[k] = lds_operand(&B[r * ldb + 4 * k + g]); }
   if (!ASSIGN) {  // the block to update travels with the operands instead of after the products
 #pragma unroll
-    for (int i = 0; i < 4; i++) cv[i] = DROID_GEMM_LD(&C[(g + 4 * i) * LDP + r]);
+    for (int i = 0; i < 4; i++) cv[i] = lds_operand(&C[(g + 4 * i) * LDP + r]);
   }
 #ifdef CHOL_STAMPS
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -255,11 +233,6 @@ __device__ __forceinline__ void wave_gemm_nt16_inl(lds_f64* Cl, const lds_f64* A
 #endif
 #pragma unroll
   for (int i = 0; i < 4; i++) C[(g + 4 * i) * LDP + r] = ASSIGN ? acc[i] : cv[i] - acc[i];
-#undef DROID_GEMM_LD
-}
-template <bool ASSIGN>
-__device__ __attribute__((noinline)) void wave_gemm_nt16(lds_f64* Cl, const lds_f64* Al, const lds_f64* Bl, int ldb) {
-  wave_gemm_nt16_inl<ASSIGN>(Cl, Al, Bl, ldb);
 }
 
 // In-register Cholesky of the 16x16 block at Lb (LDS, pitch LDP) by one wave.  Lane l < 16 holds
@@ -300,11 +273,7 @@ __device__ __forceinline__ void potrf16_pivot(double (&a)[16], double (&w)[16], 
   for (int c = J + 1; c < 16; c++) {
     // unrolled with compile-time lane numbers
     switch (c) {
-#ifdef CHOL_NO_W  // timing experiment only (wrong inverses): the column operations on the identity rows left out
-#define DROID_CASE(CC) case CC: if (CC > J) { fmac_bcast<J, CC>(a[CC], a[J], a[J]); } break;
-#else
 #define DROID_CASE(CC) case CC: if (CC > J) { fmac_bcast<J, CC>(a[CC], a[J], a[J]); fmac_bcast<J, CC>(w[CC], a[J], w[J]); } break;
-#endif
       DROID_CASE(1) DROID_CASE(2) DROID_CASE(3) DROID_CASE(4) DROID_CASE(5) DROID_CASE(6) DROID_CASE(7) DROID_CASE(8)
       DROID_CASE(9) DROID_CASE(10) DROID_CASE(11) DROID_CASE(12) DROID_CASE(13) DROID_CASE(14) DROID_CASE(15)
 #undef DROID_CASE
@@ -699,53 +668,11 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
     const gbl_f64* slot1 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, kp, k) * NB * NB;  // L[kp,k]
     const gbl_f64* slot0 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, bi, k) * NB * NB;  // L[bi,k]
     for (int sp = 0; sp < 4; sp++) {
-#ifdef CHOL_DIRECT00
-      // Candidate (i) of DESIGN section 8 (A/B build): the pivot wave takes ITS 16x16 block of the last
-      // strip -- rows 0..15 of L[kp,k], the only operand of D00's last rank-16 update -- straight from the hand-over
-      // slot into MFMA operands (8-byte sc1 loads, data-tagged like the strip loads) and applies the update in front
-      // of the barrier instead of behind it (no LDS stage on the chain for this block).
-      if (sp == 3 && wave == 0) {
-        const gbl_f64* q = slot1 + (size_t)fr * NB + 48 + fg;
-        const bool rowok = c0 + fr < n;
-        double dv[4];
-        int spins = 0;
-        while (true) {
-#pragma unroll
-          for (int kk = 0; kk < 4; kk++)
-            asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(dv[kk]) : "v"(q + 4 * kk) : "memory");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          bool there = true;
-#pragma unroll
-          for (int kk = 0; kk < 4; kk++) {
-            asm volatile("" : "+v"(dv[kk]));
-            if (rowok && __double_as_longlong(dv[kk]) == CFP_TAG) there = false;
-          }
-          if (__all(there)) break;
-          if (++spins > CFP_SPIN_LIMIT || ((spins & 255) == 0 && cfp_load(abortf) == 1)) {
-            cfp_store(abortf, 1);
-            atomicMax(fail, 2);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
-          const double x = rowok ? dv[kk] : 0.0;
-          tacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(-x, x, tacc[0], 0, 0, 0);
-        }
-      }
-#endif
       if (grp == 0) load_strip64(B1, slot1, c0, sp, c0, n, fail, abortf);
       else load_strip64(B0, slot0, r0, sp, r0, nrows, fail, abortf);
       __syncthreads();
       if (sp == 3) STAMP(1);
       if (sp == 3 && wave == 0) __builtin_amdgcn_s_setprio(3);
-#ifdef CHOL_WARM
-      if (sp == 1 && wave == 7) {  // experiment: fetch the GEMM helpers' code long before the chain calls them (B2 is not in use yet)
-        wave_gemm_nt16<true>(&B2[48 * LDP + 48], &B2[48 * LDP + 32], &B2[32 * LDP + 48], LDP);
-        wave_gemm_nt16<false>(&B2[48 * LDP + 48], &B2[48 * LDP + 32], &B2[32 * LDP + 48], LDP);
-      }
-#endif
 #pragma unroll
       for (int i = 0; i < 2; i++) {
         if (i < ntile) {
@@ -753,9 +680,6 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
           if (code[i] & 0x10) {
             if (solve_rows) block_update16(tacc[i], &B0[(16 * rg) * LDP + 16 * sp], &B1[(16 * nt) * LDP + 16 * sp]);
           } else {
-#ifdef CHOL_DIRECT00
-            if (!(sp == 3 && wave == 0))   // done in front of the barrier, from registers
-#endif
             block_update16(tacc[i], &B1[(16 * rg) * LDP + 16 * sp], &B1[(16 * nt) * LDP + 16 * sp]);
           }
         }
@@ -820,11 +744,7 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
       const int nd = 3 - p;  // diagonal-tile blocks below the pivot block
       if (wave < nd) {
         const int q = p + 1 + wave;
-#ifdef CHOL_INL_EXP
-        wave_gemm_nt16_inl<true>(&B2[(16 * q) * LDP + 16 * p], &B2[(16 * q) * LDP + 16 * p], &Wl[WLB * p], WLP);
-#else
         wave_gemm_nt16<true>(&B2[(16 * q) * LDP + 16 * p], &B2[(16 * q) * LDP + 16 * p], &Wl[WLB * p], WLP);
-#endif
       } else if (solve_rows && wave < nd + 4) {
         const int g = wave - nd;
         wave_gemm_nt16<true>(&BT[(16 * g) * LDP + 16 * p], &BT[(16 * g) * LDP + 16 * p], &Wl[WLB * p], WLP);

@@ -13,7 +13,6 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/droid_backends_hip.h"
 
@@ -150,9 +149,7 @@ struct Combine<__half, R> {
 // which made every line travel through L1/L2 2r+2 times.  Taps outside the plane are masked to 0
 // after the load (reading the neighbouring row of the same tensor is harmless); only lanes whose
 // wide load would leave the tensor fall back to per-element loads.
-#ifndef CORR_MINWG
-#define CORR_MINWG 1
-#endif
+constexpr int CORR_MINWG = 1;  // min workgroups per CU of corr_index_forward_kernel
 typedef uint32_t u32a4 __attribute__((aligned(4)));
 
 template <typename T, int NT>
@@ -321,9 +318,8 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
 template <typename T, int R>
 static bool launch_corr_small(const T* v, const float* coords, T* c, int B, int HW, int H2, int W2, size_t obs,
                               float cs, hipStream_t s) {
-  static const bool off = (getenv("DROID_CORR_NO_SMALL") != nullptr);  // diagnostics: the per-lane row-load kernel
   const int PB = H2 * W2 * (int)sizeof(T);
-  if (off || PB > CS_MAXPLANE || (PB & 15) != 0 || (reinterpret_cast<uintptr_t>(v) & 15) != 0) return false;
+  if (PB > CS_MAXPLANE || (PB & 15) != 0 || (reinterpret_cast<uintptr_t>(v) & 15) != 0) return false;
   hipLaunchKernelGGL((corr_index_forward_small<T, R>), dim3((HW + 63) / 64, B), dim3(64), 64 * (PB + 4), s, v, coords, c,
                      HW, H2, W2, obs, cs);
   return true;
@@ -464,8 +460,7 @@ static bool launch_corr_coop(const T* v, const float* coords, T* c, int B, int H
   if constexpr (R != 3 || sizeof(T) > 4) {
     return false;
   } else {
-    static const bool off = (getenv("DROID_CORR_NO_COOP") != nullptr);  // diagnostics: the per-lane row-load kernel
-    if (off || W2 * (int)sizeof(T) > 64 || (HW & 63) != 0) return false;
+    if (W2 * (int)sizeof(T) > 64 || (HW & 63) != 0) return false;
     hipLaunchKernelGGL((corr_index_forward_coop<T, R>), dim3((HW + 255) / 256, B), dim3(256), 0, s, v, coords, c, HW, H2, W2,
                        vol_elems, obs, cs);
     return true;
@@ -702,10 +697,7 @@ __global__ __launch_bounds__(256) void altcorr_forward_generic(const T* __restri
 // box does not fit (incoherent coordinates) take the per-query path of the generic kernel.
 constexpr int ALT_TQ = 8;          // tile is ALT_TQ x ALT_TQ queries
 constexpr int ALT_MAXPOS = 448;    // fmap2 positions staged per tile
-#ifndef DROID_ALT_CH
-#define DROID_ALT_CH 32
-#endif
-constexpr int ALT_CH = DROID_ALT_CH;          // channels per stage
+constexpr int ALT_CH = 32;                    // channels per stage
 constexpr int ALT_WAVES = 4;                  // waves per workgroup: wave w owns tap rows j = w (mod 4)
 constexpr int ALT_THREADS = 64 * ALT_WAVES;
 constexpr int ALT_PITCH = ALT_CH + 4;         // floats per staged position (pad keeps 16-B alignment)
@@ -1373,9 +1365,9 @@ __global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_forward_mfma(co
 // copies of the feature maps (`pyramid[i][:, jj]`).  grid (tiles, levels, E); output
 // [E, levels*(2r+1)^2, H, W] = torch.cat of the per-level results for one coordinate set.
 struct AltPyramid {
-  const void* level[4];  // [frames, H >> l, W >> l, C] fp32 or fp16, channels last
+  const float* level[4];  // [frames, H >> l, W >> l, C] fp32, channels last (half pyramids take altcorr_wave_f16)
 };
-template <int R, typename TI>
+template <int R>
 __global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_pyramid_mfma(AltPyramid pyr,
                                                                const int64_t* __restrict__ ii,
                                                                const int64_t* __restrict__ jj,
@@ -1398,8 +1390,8 @@ __global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_pyramid_mfma(Al
       for (int o = threadIdx.x >> 6; o < RD * RD; o += 4) oute[(size_t)o * H1W1 + qy * W1 + qx] = 0.f;
     return;
   }
-  const TI* lp = static_cast<const TI*>(lvl == 0 ? pyr.level[0] : (lvl == 1 ? pyr.level[1] : (lvl == 2 ? pyr.level[2] : pyr.level[3])));
-  altcorr_mfma_body<R, TI, float>(static_cast<const TI*>(pyr.level[0]) + (size_t)fi * H1W1 * C, lp + (size_t)fj * H2 * W2 * C,
+  const float* lp = lvl == 0 ? pyr.level[0] : (lvl == 1 ? pyr.level[1] : (lvl == 2 ? pyr.level[2] : pyr.level[3]));
+  altcorr_mfma_body<R, float, float>(pyr.level[0] + (size_t)fi * H1W1 * C, lp + (size_t)fj * H2 * W2 * C,
                        coords + (size_t)e * H1W1 * 2, 1.0f / (float)(1 << lvl), oute, tile, H1, W1, H2, W2, C);
 }
 
@@ -1730,7 +1722,7 @@ int launch_altcorr_forward(const void* f1, const void* f2, const float* coords, 
   }
   // half maps (altcorr_kernel.cu:308 dispatches half): f16 matrix cores, fp32 accumulation, half output
   if (dtype == DROID_F16 && (C % 32) == 0 && C <= 128 && (r == 3 || r == 4) && (long)H2 * W2 * C < (1l << 30) &&
-      (long)H1 * W1 * C < (1l << 30) && !getenv("DROID_ALTCORR_F16_WG")) {
+      (long)H1 * W1 * C < (1l << 30)) {
     AwArgs a{};
     a.f1 = static_cast<const __half*>(f1);
     a.f2[0] = static_cast<const __half*>(f2);
@@ -1780,11 +1772,7 @@ int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t*
   if (nlevels < 1 || nlevels > 4 || (r != 3 && r != 4) || (C % ch) != 0 || C > 128) return DROID_E_ARG;
   if ((H >> (nlevels - 1)) < 1 || (W >> (nlevels - 1)) < 1 || (long)H * W * C >= (1l << 30)) return DROID_E_ARG;
   if ((long)E * nlevels > 65535) return DROID_E_ARG;
-  AltPyramid pyr;
-  for (int l = 0; l < 4; l++) pyr.level[l] = levels_dev[l < nlevels ? l : nlevels - 1];
-  const int tiles = ((W + AM_TX - 1) / AM_TX) * ((H + AM_TY - 1) / AM_TY);
-  dim3 grid(tiles, nlevels, E), block(256);
-  if (dtype == DROID_F16 && !getenv("DROID_ALTCORR_F16_WG")) {
+  if (dtype == DROID_F16) {
     AwArgs a{};
     a.f1 = static_cast<const __half*>(levels_dev[0]);
     for (int l = 0; l < nlevels; l++) {
@@ -1795,15 +1783,14 @@ int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t*
     a.frames = frames; a.N = 1; a.H1 = H; a.W1 = W; a.C = C; a.nlevels = nlevels;
     return launch_altcorr_wave_f16<float>(a, r, E, s);
   }
-  if (dtype == DROID_F16) {
-    if (r == 3)
-      hipLaunchKernelGGL((altcorr_pyramid_mfma<3, __half>), grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
-    else
-      hipLaunchKernelGGL((altcorr_pyramid_mfma<4, __half>), grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
-  } else if (r == 3)
-    hipLaunchKernelGGL((altcorr_pyramid_mfma<3, float>), grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
+  AltPyramid pyr;
+  for (int l = 0; l < 4; l++) pyr.level[l] = static_cast<const float*>(levels_dev[l < nlevels ? l : nlevels - 1]);
+  const int tiles = ((W + AM_TX - 1) / AM_TX) * ((H + AM_TY - 1) / AM_TY);
+  dim3 grid(tiles, nlevels, E), block(256);
+  if (r == 3)
+    hipLaunchKernelGGL(altcorr_pyramid_mfma<3>, grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
   else
-    hipLaunchKernelGGL((altcorr_pyramid_mfma<4, float>), grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
+    hipLaunchKernelGGL(altcorr_pyramid_mfma<4>, grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
   return 0;
 }
 
@@ -2024,8 +2011,7 @@ int launch_altcorr_backward(const float* f1, const float* f2, const float* coord
                             int W1, int H2, int W2, int C, int r, hipStream_t s) {
   if (B > 65535 || N > 65535) return DROID_E_ARG;
   const int HW = H1 * W1;
-  static const bool per_tap = (getenv("DROID_ALTCORR_BWD_PER_TAP") != nullptr);  // diagnostics: the old kernel
-  if (!per_tap && (C % AB_CH) == 0 && (r == 3 || r == 4)) {
+  if ((C % AB_CH) == 0 && (r == 3 || r == 4)) {
     const int tiles = ((W1 + ABT - 1) / ABT) * ((H1 + ABT - 1) / ABT);
     if (r == 3)
       hipLaunchKernelGGL((altcorr_backward_tiled<3>), dim3(tiles, N, B), dim3(256), 0, s, f1, f2, coords, corr_grad, f1g,

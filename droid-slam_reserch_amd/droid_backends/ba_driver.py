@@ -108,22 +108,6 @@ class HipBackend:
         self.packed = self.ws[off:off + nel.value * 8].view(torch.float64)   # lower triangle + rhs row, contiguous
         self.dx = torch.empty((t1 - t0, 6), dtype=torch.float32, device=p.poses.device)
         self.dz = torch.empty((M, H * W), dtype=torch.float32, device=p.poses.device)
-        self._ridx_key = (t1 - t0, nel_sys.value)   # PITCHED element count: reduce_index derives the row pitch from it
-
-    def reduce_index(self):
-        """Flat indices of the entries of `system` that the solve reads: the lower triangle of the
-        6P x 6P matrix plus the rhs row (include/droid_backends_hip.h: rows of `ld` doubles).  The
-        sharded driver all-reduces only these (half the bytes of the dense buffer)."""
-        P, nel = self._ridx_key
-        cache = getattr(self, "_ridx", None)
-        if cache is None or cache[0] != self._ridx_key or cache[1].device != self.system.device:
-            n = 6 * P
-            ld = nel // (n + 1)
-            r = torch.arange(n + 1, device=self.system.device).view(-1, 1)
-            c = torch.arange(ld, device=self.system.device).view(1, -1)
-            idx = ((c <= r) & (c < n)).flatten().nonzero().squeeze(1)
-            self._ridx = cache = (self._ridx_key, idx)
-        return cache[1]
 
     def build(self, p: BAProblemDev, motion_only):
         E, nbuf, H, W, M, t0, t1 = self._dims

@@ -1,4 +1,4 @@
-"""Timing of altcorr_backward (level 0, 48x64, C=128, 32 edges): tiled LDS kernel vs DROID_ALTCORR_BWD_PER_TAP=1."""
+"""Timing of altcorr_backward, tiled LDS kernel (levels 0 and 2 of 48x64, C=128, 32 edges)."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "droid-slam_reserch_amd")]
