@@ -333,21 +333,29 @@ int droid_ba_unpack_chunk(int E, int nbuf, int H, int W, int M, int t0, int t1, 
   return check_hip("ba_unpack_chunk");
 }
 
+// the pointers droid_ba_solve_update and droid_ba_solve_update_overlap read
+static int solve_update_check(const float* poses, const float* disps, const float* intrinsics, const float* weights,
+                              const int64_t* ii, const int64_t* jj, int E, int motion_only) {
+  if (!poses || !disps) return fail(DROID_E_ARG, "ba: null %s", "state pointer");
+  if (!motion_only && (!intrinsics || (E > 0 && (!weights || !ii || !jj))))
+    return fail(DROID_E_ARG, "ba: null %s", "intrinsics/weights/edges");
+  return DROID_OK;
+}
+
 int droid_ba_solve_update_overlap(float* poses, float* disps, const float* intrinsics, const float* weights,
                                   const int64_t* ii, const int64_t* jj, int E, int nbuf, int H, int W, int M,
                                   int t0, int t1, int epoch, int motion_only, float* dx_out, float* dz_out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
   int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  if (!rc) rc = solve_update_check(poses, disps, intrinsics, weights, ii, jj, E, motion_only);
   if (rc) return rc;
-  if (!poses || !disps) return fail(DROID_E_ARG, "ba: null %s", "state pointer");
-  if (!motion_only && (!intrinsics || (E > 0 && (!weights || !ii || !jj))))
-    return fail(DROID_E_ARG, "ba: null %s", "intrinsics/weights/edges");
   if (E <= 0 || epoch <= 0) return fail(DROID_E_ARG, "ba_solve_update_overlap: needs %s", "edges (the build presets the solver scratch) and epoch > 0");
   hipStream_t s = (hipStream_t)stream;
-  if (!launch_chol_factor_overlap(v.sys, v.n, v.ld, v.hdr + HDR_CHOL_FAIL, v.bs_flags, v.ldiag, v.ov_ready, epoch, s))
+  const CholSystem c(v);
+  if (!launch_chol_factor_overlap(c, v.ov_ready, epoch, s))
     return fail(DROID_E_ARG, "ba_solve_update_overlap: %s", "the single-launch solver is not available for this system (unpack and call droid_ba_solve_update)");
-  launch_chol_backsolve(v.sys, v.n, v.ld, v.xsol, v.bs_flags, v.ldiag, v.hdr + HDR_CHOL_FAIL, s, true);
+  launch_chol_backsolve(c, true, s);
   launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, dx_out, dz_out, motion_only != 0, s,
                 mirror_of(workspace));
   return check_hip("ba_solve_update_overlap");
@@ -359,16 +367,11 @@ int droid_ba_solve_update(float* poses, float* disps, const float* intrinsics, c
                           float* dz_out, void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
   int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  if (!rc) rc = solve_update_check(poses, disps, intrinsics, weights, ii, jj, E, motion_only);
   if (rc) return rc;
-  if (!poses || !disps) return fail(DROID_E_ARG, "ba: null %s", "state pointer");
-  if (!motion_only && (!intrinsics || (E > 0 && (!weights || !ii || !jj))))
-    return fail(DROID_E_ARG, "ba: null %s", "intrinsics/weights/edges");
   hipStream_t s = (hipStream_t)stream;
-  // with edges, droid_ba_build's assemble kernel has preset the solver scratch and cleared the failure flag
-  const bool preset = E > 0;
-  if (!preset) (void)hipMemsetAsync(v.hdr + HDR_CHOL_FAIL, 0, sizeof(int), s);
-  launch_chol_solve(v.sys, v.n, v.ld, (double)lm, (double)ep, v.xsol, v.hdr + HDR_CHOL_FAIL, v.bs_flags, v.ldiag, s,
-                    preset);
+  // with edges, droid_ba_build's assemble kernel has preset the solver scratch
+  launch_chol_solve(CholSystem(v), (double)lm, (double)ep, s, E > 0);
   launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, dx_out, dz_out, motion_only != 0, s,
                 mirror_of(workspace));
   return check_hip("ba_solve_update");
@@ -395,7 +398,7 @@ int droid_ba(float* poses, float* disps, const float* intrinsics, const float* d
 
 // Measurement support: one Gauss-Newton iteration (after droid_ba_prepare) with a HIP event
 // between kernel groups on `stream`; blocks until done.  stage_ms[8] = {memset+linearise,
-// assemble, fused E-rows + Schur SYRK + rhs, (unused), damp+factor, back-substitution solve, dx/disps/poses update, total}.
+// assemble, fused E-rows + Schur SYRK + rhs, (unused: 0), damp+factor, back-substitution solve, dx/disps/poses update, total}.
 int droid_ba_profile_iteration(float* poses, float* disps, const float* intrinsics,
                                const float* disps_sens, const float* targets, const float* weights,
                                const float* eta, const int64_t* ii, const int64_t* jj, int E,
@@ -408,32 +411,25 @@ int droid_ba_profile_iteration(float* poses, float* disps, const float* intrinsi
   hints_of(v, workspace, false);
   if (!stage_ms) return fail(DROID_E_ARG, "ba_profile: null %s", "stage_ms");
   hipStream_t s = (hipStream_t)stream;
-  hipEvent_t ev[8];
+  hipEvent_t ev[7];
   for (auto& e : ev) (void)hipEventCreate(&e);
   (void)hipEventRecord(ev[0], s);
-  launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, 0, s);
-  (void)hipEventRecord(ev[1], s);
-  launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, 1, s);
-  (void)hipEventRecord(ev[2], s);
-  launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, 2, s);
-  (void)hipEventRecord(ev[3], s);
-  launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, 3, s);
-  (void)hipEventRecord(ev[4], s);
-  if (E <= 0) (void)hipMemsetAsync(v.hdr + HDR_CHOL_FAIL, 0, sizeof(int), s);
-  if (v.n > 0 && E <= 0) {  // presets of x and the hand-off flags (with edges the assemble kernel did it)
-    (void)hipMemsetAsync(v.xsol, 0xFF, sizeof(double) * (size_t)v.n, s);
-    (void)hipMemsetAsync(v.bs_flags, 0xFF, sizeof(int) * chol_flag_words(v.n), s);
-    (void)hipMemsetAsync(v.ldiag + chol_lfin_offset(v.n), 0xFF, sizeof(double) * chol_tiles(v.n) * CHOL_NB * CHOL_NB, s);
+  for (int stage = 0; stage < 3; stage++) {   // launch_build, stage by stage
+    launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, stage, s);
+    (void)hipEventRecord(ev[stage + 1], s);
   }
-  const bool single = launch_chol_factor(v.sys, v.n, v.ld, (double)lm, (double)ep, v.hdr + HDR_CHOL_FAIL, v.bs_flags, v.ldiag, s);
+  const CholSystem c(v);   // launch_chol_solve as droid_ba_solve_update calls it, with an event between its halves
+  if (E <= 0) launch_chol_preset(c, s);
+  const bool single = launch_chol_factor(c, (double)lm, (double)ep, s);
+  (void)hipEventRecord(ev[4], s);
+  launch_chol_backsolve(c, single, s);
   (void)hipEventRecord(ev[5], s);
-  launch_chol_backsolve(v.sys, v.n, v.ld, v.xsol, v.bs_flags, v.ldiag, v.hdr + HDR_CHOL_FAIL, s, single);
-  (void)hipEventRecord(ev[6], s);
   launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, nullptr, nullptr, motion_only != 0, s);
-  (void)hipEventRecord(ev[7], s);
-  hipError_t e = hipEventSynchronize(ev[7]);
-  for (int k = 0; k < 7; k++) (void)hipEventElapsedTime(&stage_ms[k], ev[k], ev[k + 1]);
-  (void)hipEventElapsedTime(&stage_ms[7], ev[0], ev[7]);
+  (void)hipEventRecord(ev[6], s);
+  hipError_t e = hipEventSynchronize(ev[6]);
+  stage_ms[3] = 0.0f;
+  for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&stage_ms[k < 3 ? k : k + 1], ev[k], ev[k + 1]);
+  (void)hipEventElapsedTime(&stage_ms[7], ev[0], ev[6]);
   for (auto& x : ev) (void)hipEventDestroy(x);
   if (e != hipSuccess) {
     snprintf(g_err, sizeof(g_err), "ba_profile: %s", hipGetErrorString(e));
@@ -484,21 +480,15 @@ int droid_ba_attach_status_mirror(const void* workspace, int* mirror) {
   return DROID_OK;
 }
 
-size_t droid_chol_scratch_doubles(int n) {
-  if (n <= 0) return 0;
-  return (size_t)(n + 1) * chol_ld(n) + chol_ldiag_doubles(n) + (chol_flag_words(n) + 1) / 2 + 16;
-}
+size_t droid_chol_scratch_doubles(int n) { return CholSystem::scratch_doubles(n); }
 
 int droid_chol_solve(const double* A, const double* b, double* x, int n, double* scratch,
                      int* fail_flag, void* stream) {
   if (n <= 0 || !A || !b || !x || !scratch || !fail_flag) return fail(DROID_E_ARG, "chol_solve: bad %s", "argument");
   hipStream_t s = (hipStream_t)stream;
-  const int ld = chol_ld(n);
-  (void)hipMemsetAsync(fail_flag, 0, sizeof(int), s);
-  launch_chol_pack(A, b, scratch, n, ld, s);
-  double* ldiag = scratch + (size_t)(n + 1) * ld;   // tail of the scratch buffer: diagonal tiles, then flags
-  int* flags = reinterpret_cast<int*>(ldiag + chol_ldiag_doubles(n));
-  launch_chol_solve(scratch, n, ld, 0.0, 0.0, x, fail_flag, flags, ldiag, s);
+  const CholSystem c(scratch, n, x, fail_flag);
+  launch_chol_pack(A, b, c.S, c.n, c.ld, s);
+  launch_chol_solve(c, 0.0, 0.0, s, false);
   return check_hip("chol_solve");
 }
 

@@ -200,13 +200,27 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
 
 // 4-byte words from xsol through the end of bs_flags (contiguous in the workspace): what one iteration's solve
 // expects preset to 0xFF bytes.  With edges, the assemble kernel's spare workgroups do it (and zero the failure
-// flag); without, droid_ba_solve_update falls back to fills.
+// flag); without, launch_chol_preset's fills do.
 __host__ __device__ inline int solver_preset_words(const BaView& v) {
   return (int)((reinterpret_cast<const char*>(v.bs_flags) - reinterpret_cast<const char*>(v.xsol)) / 4 +
                (long)chol_flag_words(v.n));
 }
 // 32 KB blocks of the panel-tile hand-over slots (ldiag + chol_lfin_offset), preset to 0xFF bytes the same way
 __host__ __device__ inline int solver_preset_tiles(const BaView& v) { return v.n > 0 ? (int)chol_tiles(v.n) : 0; }
+
+// What one Cholesky solve works on: the augmented system S ((n+1) x ld, row n = rhs, factored in place), the
+// solution x [n], the scratch of the single-launch kernels (flags [chol_flag_words(n)], ldiag [chol_ldiag_doubles(n)])
+// and the failure word (1: not positive definite, 2: stalled grid).  Every solve expects x, the flags and the
+// hand-over slots of ldiag preset to 0xFF bytes and the failure word to 0: by launch_chol_preset, or in the BA by the
+// assemble kernel (above).
+struct CholSystem {
+  double* S; int n, ld; double* x; int* flags; double* ldiag; int* fail;
+  explicit CholSystem(const BaView& v)
+      : S(v.sys), n(v.n), ld(v.ld), x(v.xsol), flags(v.bs_flags), ldiag(v.ldiag), fail(v.hdr + HDR_CHOL_FAIL) {}
+  // droid_chol_solve: S, ldiag and the flags carved out of one scratch buffer of scratch_doubles(n) doubles
+  CholSystem(double* scratch, int n, double* x, int* fail);
+  static size_t scratch_doubles(int n);
+};
 
 // kernels' launchers (ba_kernels.hip / chol.hip)
 void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStream_t s);
@@ -215,7 +229,7 @@ void launch_unpack_system(const BaView& v, hipStream_t s);
 void launch_build(const BaView& v, const float* poses, const float* disps, const float* intr,
                   const float* sens, const float* targets, const float* weights, const float* eta,
                   const int64_t* ii, const int64_t* jj, bool motion_only, hipStream_t s);
-// stage: 0 memset+linearise, 1 assemble, 2 schur, 3 ev (measurement support)
+// stage: 0 memset+linearise, 1 assemble, 2 schur (measurement support)
 void launch_build_stage(const BaView& v, const float* poses, const float* disps, const float* intr,
                         const float* sens, const float* targets, const float* weights,
                         const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only,
@@ -224,22 +238,18 @@ void launch_build_stage(const BaView& v, const float* poses, const float* disps,
 void launch_update(const BaView& v, float* poses, float* disps, const float* intr, const float* weights,
                    const int64_t* ii, const int64_t* jj, const double* x, float* dx_out, float* dz_out,
                    bool motion_only, hipStream_t s, int* status_mirror = nullptr);
-// In-place damped Cholesky of the lower triangle of sys ((n+1) x ld, row n = rhs) + solve -> x [n].
-// flags [chol_flag_words(n)] and ldiag [chol_ldiag_doubles(n)]: scratch of the single-launch factorisation
-// (null: one launch per block column).  launch_chol_solve presets x and flags itself unless told that it has
-// been done; callers of the two halves preset them with 0xFF bytes before launch_chol_factor.
-void launch_chol_solve(double* sys, int n, int ld, double lm, double ep, double* x, int* fail_flag,
-                       int* flags, double* ldiag, hipStream_t s, bool preset_done = false);
+// The Cholesky solve of a CholSystem (chol.hip), damped: diag += ep + lm * diag.  launch_chol_solve = the preset
+// (unless done), launch_chol_factor, launch_chol_backsolve; launch_chol_factor returns whether the single-launch
+// kernel ran, and launch_chol_backsolve needs that answer.
+void launch_chol_preset(const CholSystem& c, hipStream_t s);
+bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s);
+void launch_chol_backsolve(const CholSystem& c, bool factor_single, hipStream_t s);
+void launch_chol_solve(const CholSystem& c, double lm, double ep, hipStream_t s, bool preset_done);
 
 // Overlap mode (multi-GPU): block columns [J0, J1) of the all-reduced packed system -> pitched matrix, damped; then
-// ready[J0..J1) = epoch for the factorisation that is already running (launch_chol_factor_overlap).
+// ready[J0..J1) = epoch for the factorisation that is already running.  launch_chol_factor_overlap starts that
+// single-launch factorisation (false: not available for this system); launch_chol_backsolve(c, true, s) follows it.
 void launch_unpack_cols(const BaView& v, int J0, int J1, double lm, double ep, int epoch, hipStream_t s);
-bool launch_chol_factor_overlap(double* sys, int n, int ld, int* fail_flag, int* flags, double* ldiag,
-                                const int* ready, int epoch, hipStream_t s);
-// launch_chol_factor returns whether the single-launch kernel ran; pass that to launch_chol_backsolve
-bool launch_chol_factor(double* sys, int n, int ld, double lm, double ep, int* fail_flag, int* flags,
-                        double* ldiag, hipStream_t s);
-void launch_chol_backsolve(double* sys, int n, int ld, double* x, int* flags, double* ldiag, int* err,
-                           hipStream_t s, bool factor_single);
+bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s);
 
 }  // namespace droid

@@ -2125,15 +2125,13 @@ void launch_build_stage(const BaView& v, const float* poses, const float* disps,
         }
       }
       break;
-    case 3:
-      break;
   }
 }
 
 void launch_build(const BaView& v, const float* poses, const float* disps, const float* intr,
                   const float* sens, const float* targets, const float* weights, const float* eta,
                   const int64_t* ii, const int64_t* jj, bool motion_only, hipStream_t s) {
-  for (int stage = 0; stage < 4; stage++)
+  for (int stage = 0; stage < 3; stage++)
     launch_build_stage(v, poses, disps, intr, sens, targets, weights, eta, ii, jj, motion_only, stage, s);
 }
 

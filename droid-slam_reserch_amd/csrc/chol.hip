@@ -1385,9 +1385,32 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
   }
 }
 
-// Single-launch path: needs the hand-off flags, the side buffer for the factored diagonal tiles,
-// 128-byte aligned rows (no cache line shared between tiles of different workgroups) and a grid
-// that is resident as a whole.
+// ---- host side: the launchers of a CholSystem (ba_internal.hpp) ------------------------------------------------
+// launch_chol_factor: the single-launch kernel where chol_single_launch allows it, else one chol_step_kernel per block
+// column.  launch_chol_backsolve: the persistent kernel for 2 .. BSP_MAX_BLOCKS block columns (FAST after a
+// single-launch factorisation: it reads L_jj from `ldiag`), else one chol_backsolve_kernel per block column, which
+// reads L_jj from the matrix: after a single-launch factorisation chol_ldiag_to_sys_kernel first copies them back.
+
+// Diagnostic and test switches of the solver, read once per process.
+struct CholSwitches {
+  bool multi_launch;       // DROID_CHOL_MULTI_LAUNCH: the per-step kernels only
+  bool cooperative;        // DROID_CHOL_COOPERATIVE=1: persistent grids through hipLaunchCooperativeKernel (see below)
+  bool force_bs_refusal;   // DROID_CHOL_FORCE_BS_REFUSAL: the cooperative back-substitution counts as refused
+  int grid;                // DROID_CHOL_GRID: cap of the factorisation grid (taken when >= 8 and below the residency)
+  int overlap_reserve;     // DROID_OVERLAP_RESERVE_CUS (default 32): CUs the overlap factorisation leaves free
+};
+static const CholSwitches& chol_switches() {
+  static const CholSwitches sw = {
+      getenv("DROID_CHOL_MULTI_LAUNCH") != nullptr,
+      getenv("DROID_CHOL_COOPERATIVE") != nullptr && atoi(getenv("DROID_CHOL_COOPERATIVE")) != 0,
+      getenv("DROID_CHOL_FORCE_BS_REFUSAL") != nullptr,
+      getenv("DROID_CHOL_GRID") ? atoi(getenv("DROID_CHOL_GRID")) : 0,
+      getenv("DROID_OVERLAP_RESERVE_CUS") ? atoi(getenv("DROID_OVERLAP_RESERVE_CUS")) : 32};
+  return sw;
+}
+
+// Single-launch path: needs 128-byte aligned rows (no cache line shared between tiles of different workgroups) and a
+// grid that is resident as a whole.
 static int chol_resident_workgroups() {
   static int cached = -1;
   if (cached < 0) {
@@ -1402,15 +1425,16 @@ static int chol_resident_workgroups() {
   return cached;
 }
 
-static bool chol_single_launch(const double* sys, int n, int ld, const int* flags, const double* ldiag) {
-  static const bool off = (getenv("DROID_CHOL_MULTI_LAUNCH") != nullptr);  // diagnostics: the per-step path
-  const int nb = (n + NB - 1) / NB;
+static bool chol_single_launch(const CholSystem& c) {
+  const int nb = (c.n + NB - 1) / NB;
   // beyond ~10 tiles per resident workgroup (n ~ 4400 on 256 CUs) the trailing updates, serialised inside the
   // persistent workgroups, outweigh the saved kernel boundaries (measured cross-over: n = 4500)
-  return !off && flags != nullptr && ldiag != nullptr && nb >= 2 && (ld % 16) == 0 &&
-         (reinterpret_cast<uintptr_t>(sys) % 128) == 0 && chol_resident_workgroups() >= 8 &&
-         chol_tiles(n) <= (size_t)10 * chol_resident_workgroups();
+  return !chol_switches().multi_launch && nb >= 2 && (c.ld % 16) == 0 && (reinterpret_cast<uintptr_t>(c.S) % 128) == 0 &&
+         chol_resident_workgroups() >= 8 && chol_tiles(c.n) <= (size_t)10 * chol_resident_workgroups();
 }
+
+// grid of a single-launch factorisation: one workgroup per tile, `cap` at most
+static int chol_factor_grid(int n, int cap) { return chol_tiles(n) < (size_t)cap ? (int)chol_tiles(n) : cap; }
 
 // ---- residency of the single-launch kernels ------------------------------------------------------------------
 // Both persistent kernels spin across workgroups, so their whole grid must be resident.  A plain launch gives that
@@ -1452,8 +1476,7 @@ static std::unique_lock<std::mutex> persist_enter(hipStream_t s) {
 
 // The single-launch factorisation leaves the factored diagonal tiles L_jj in the side buffer `ldiag`, not in the
 // matrix (the other panel workgroups still read the unfactored tile).  The per-step back-substitution reads them from
-// the matrix: this copies the lower triangles back when that kernel has to follow a single-launch factorisation
-// (cooperative launch of the back-substitution refused).
+// the matrix: this copies the lower triangles back whenever that kernel follows a single-launch factorisation.
 __global__ __launch_bounds__(256) void chol_ldiag_to_sys_kernel(double* __restrict__ S, int n, int ld,
                                                                 const double* __restrict__ Ldiag) {
   const int j = blockIdx.x, c0 = j * NB, wk = min(NB, n - c0);
@@ -1463,120 +1486,108 @@ __global__ __launch_bounds__(256) void chol_ldiag_to_sys_kernel(double* __restri
   }
 }
 
-static bool chol_cooperative() {
-  static const bool on = (getenv("DROID_CHOL_COOPERATIVE") != nullptr && atoi(getenv("DROID_CHOL_COOPERATIVE")) != 0);
-  return on;
-}
-
-// returns true when the single-launch kernel ran (the back-substitution may then use what it left in `ldiag`)
-// Overlap mode: the single-launch kernel only (returns false when it cannot be used: the caller then unpacks the
-// whole system and solves the ordinary way).  `ready` [block columns] / `epoch`: see the kernel.  The grid leaves
-// `reserve` CUs free for the collective and the unpack kernels (DROID_OVERLAP_RESERVE_CUS, default 32).
-bool launch_chol_factor_overlap(double* sys, int n, int ld, int* fail_flag, int* flags, double* ldiag,
-                                const int* ready, int epoch, hipStream_t s) {
-  if (n <= 0 || !ready || chol_cooperative() || !chol_single_launch(sys, n, ld, flags, ldiag)) return false;
-  const int nb = (n + NB - 1) / NB, nrb = (n + 1 + NB - 1) / NB;
-  int total = 0;
-  for (int j = 0; j < nb; j++) total += nrb - j;
-  static const int reserve = getenv("DROID_OVERLAP_RESERVE_CUS") ? atoi(getenv("DROID_OVERLAP_RESERVE_CUS")) : 32;
-  int cap = chol_resident_workgroups() - (reserve > 0 ? reserve : 0);
-  if (cap < 8 || (size_t)total > (size_t)10 * cap) return false;
-  const int grid = total < cap ? total : cap;
+// Overlap mode: the single-launch kernel only (false when it cannot be used: the caller then unpacks the whole system
+// and solves the ordinary way).  `ready` [block columns] / `epoch`: see the kernel.  The grid leaves
+// `overlap_reserve` CUs free for the collective and the unpack kernels.
+bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s) {
+  const CholSwitches& sw = chol_switches();
+  if (c.n <= 0 || !ready || sw.cooperative || !chol_single_launch(c)) return false;
+  const int cap = chol_resident_workgroups() - (sw.overlap_reserve > 0 ? sw.overlap_reserve : 0);
+  if (cap < 8 || chol_tiles(c.n) > (size_t)10 * cap) return false;
   auto lock = persist_enter(s);
   const double zero = 0.0;
-  hipLaunchKernelGGL(chol_factor_persistent_kernel<true>, dim3(grid), dim3(512), 0, s, sys, n, ld, fail_flag, zero, zero,
-                     flags, ldiag, ready, epoch);
+  hipLaunchKernelGGL(chol_factor_persistent_kernel<true>, dim3(chol_factor_grid(c.n, cap)), dim3(512), 0, s, c.S, c.n,
+                     c.ld, c.fail, zero, zero, c.flags, c.ldiag, ready, epoch);
   return true;
 }
 
-bool launch_chol_factor(double* sys, int n, int ld, double lm, double ep, int* fail_flag, int* flags,
-                        double* ldiag, hipStream_t s) {
-  if (n <= 0) return false;
-  const int nb = (n + NB - 1) / NB;        // block columns
-  const int nrb = (n + 1 + NB - 1) / NB;   // block rows (row n = rhs)
-  if (chol_single_launch(sys, n, ld, flags, ldiag)) {
-    int total = 0;
-    for (int j = 0; j < nb; j++) total += nrb - j;
+bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s) {
+  if (c.n <= 0) return false;
+  const CholSwitches& sw = chol_switches();
+  if (chol_single_launch(c)) {
     int cap = chol_resident_workgroups();
-    static const int env_cap = getenv("DROID_CHOL_GRID") ? atoi(getenv("DROID_CHOL_GRID")) : 0;  // diagnostics
-    if (env_cap >= 8 && env_cap < cap) cap = env_cap;
-    const int grid = total < cap ? total : cap;
+    if (sw.grid >= 8 && sw.grid < cap) cap = sw.grid;
+    const dim3 grid(chol_factor_grid(c.n, cap));
+    CholSystem a = c;
+    const int* no_ready = nullptr;
+    int no_epoch = 0;
+    void* args[] = {&a.S, &a.n, &a.ld, &a.fail, &lm, &ep, &a.flags, &a.ldiag, &no_ready, &no_epoch};
+    const void* fn = (const void*)chol_factor_persistent_kernel<false>;
     auto lock = persist_enter(s);
-    if (chol_cooperative()) {
-      const int* no_ready = nullptr;
-      int no_epoch = 0;
-      void* args[] = {&sys, &n, &ld, &fail_flag, &lm, &ep, &flags, &ldiag, &no_ready, &no_epoch};
-      if (hipLaunchCooperativeKernel((const void*)chol_factor_persistent_kernel<false>, dim3(grid), dim3(512), args, 0, s) == hipSuccess)
-        return true;
-      (void)hipGetLastError();  // refused (grid cannot be resident now): per-step kernels below
-    } else {
-      hipLaunchKernelGGL(chol_factor_persistent_kernel<false>, dim3(grid), dim3(512), 0, s, sys, n, ld, fail_flag, lm,
-                         ep, flags, ldiag, (const int*)nullptr, 0);
+    if (!sw.cooperative) {
+      (void)hipLaunchKernel(fn, grid, dim3(512), args, 0, s);
       return true;
     }
+    if (hipLaunchCooperativeKernel(fn, grid, dim3(512), args, 0, s) == hipSuccess) return true;
+    (void)hipGetLastError();  // refused (grid cannot be resident now): per-step kernels below
   }
+  const int nb = (c.n + NB - 1) / NB;        // block columns
+  const int nrb = (c.n + 1 + NB - 1) / NB;   // block rows (row n = rhs)
   for (int k = -1; k + 1 < nb; k++)         // launch k finishes panel k+1; launch -1 also damps
-    hipLaunchKernelGGL(chol_step_kernel, dim3(nrb - k - 1, k < 0 ? 2 : nb - k - 1), dim3(512), 0, s, sys, n,
-                       ld, k, fail_flag, lm, ep);
+    hipLaunchKernelGGL(chol_step_kernel, dim3(nrb - k - 1, k < 0 ? 2 : nb - k - 1), dim3(512), 0, s, c.S, c.n,
+                       c.ld, k, c.fail, lm, ep);
   return false;
 }
 
-void launch_chol_backsolve(double* sys, int n, int ld, double* x, int* flags, double* ldiag, int* err,
-                           hipStream_t s, bool factor_single) {
-  const int nb = (n + NB - 1) / NB;
-  if (flags != nullptr && nb >= 2 && nb <= BSP_MAX_BLOCKS) {
-    auto lock = persist_enter(s);
-    double* ld_arg = factor_single ? ldiag : nullptr;
+void launch_chol_backsolve(const CholSystem& c, bool factor_single, hipStream_t s) {
+  const int nb = (c.n + NB - 1) / NB;
+  if (nb >= 2 && nb <= BSP_MAX_BLOCKS) {
+    const CholSwitches& sw = chol_switches();
+    CholSystem a = c;
+    const double* ld_arg = factor_single ? c.ldiag : nullptr;
+    void* args[] = {&a.S, &a.n, &a.ld, &a.x, &a.fail, &ld_arg};
     const void* fn = factor_single ? (const void*)chol_backsolve_persistent_kernel<true>
                                    : (const void*)chol_backsolve_persistent_kernel<false>;
-    if (chol_cooperative()) {
-      void* args[] = {&sys, &n, &ld, &x, &err, &ld_arg};
-      static const bool force_refusal = getenv("DROID_CHOL_FORCE_BS_REFUSAL") != nullptr;   // test switch
-      if (!force_refusal && hipLaunchCooperativeKernel(fn, dim3(nb), dim3(256), args, 0, s) == hipSuccess) return;
-      (void)hipGetLastError();
-      // refused: the per-step kernels below run (`x` carries the sentinel preset, they overwrite all of it).  After a
-      // single-launch factorisation the diagonal tiles must first come back from the side buffer.
-      if (factor_single)
-        hipLaunchKernelGGL(chol_ldiag_to_sys_kernel, dim3(nb), dim3(256), 0, s, sys, n, ld, ldiag);
-    } else {
-      if (factor_single)
-        hipLaunchKernelGGL(chol_backsolve_persistent_kernel<true>, dim3(nb), dim3(256), 0, s, sys, n, ld, x, err, ldiag);
-      else
-        hipLaunchKernelGGL(chol_backsolve_persistent_kernel<false>, dim3(nb), dim3(256), 0, s, sys, n, ld, x, err,
-                           nullptr);
+    auto lock = persist_enter(s);
+    if (!sw.cooperative) {
+      (void)hipLaunchKernel(fn, dim3(nb), dim3(256), args, 0, s);
       return;
     }
+    if (!sw.force_bs_refusal && hipLaunchCooperativeKernel(fn, dim3(nb), dim3(256), args, 0, s) == hipSuccess) return;
+    (void)hipGetLastError();  // refused: the per-step kernels below (`x` carries the sentinel preset, they overwrite all of it)
   }
+  if (factor_single)
+    hipLaunchKernelGGL(chol_ldiag_to_sys_kernel, dim3(nb), dim3(256), 0, s, c.S, c.n, c.ld, c.ldiag);
   for (int k = nb - 1; k >= 0; k--) {
     const int c0 = k * NB;
-    hipLaunchKernelGGL(chol_backsolve_kernel, dim3(1 + (c0 + 255) / 256), dim3(256), 0, s, sys, n,
-                       ld, k, x);
+    hipLaunchKernelGGL(chol_backsolve_kernel, dim3(1 + (c0 + 255) / 256), dim3(256), 0, s, c.S, c.n,
+                       c.ld, k, c.x);
   }
 }
 
-// x [n] and flags [chol_flag_words(n)] are pre-set to 0xFF bytes here ("nothing published yet"); when the
-// flags directly follow x (BA workspace) one fill covers both.
-void launch_chol_solve(double* sys, int n, int ld, double lm, double ep, double* x, int* fail_flag,
-                       int* flags, double* ldiag, hipStream_t s, bool preset_done) {
-  if (n <= 0) return;
-  if (preset_done) {
-    const bool single = launch_chol_factor(sys, n, ld, lm, ep, fail_flag, flags, ldiag, s);
-    launch_chol_backsolve(sys, n, ld, x, flags, ldiag, fail_flag, s, single);
-    return;
-  }
-  if (ldiag)  // hand-over slots of the panel tiles: data-tagged, 0xFF bytes = not there yet
-    (void)hipMemsetAsync(ldiag + chol_lfin_offset(n), 0xFF, sizeof(double) * chol_tiles(n) * NB * NB, s);
-  const size_t xbytes = sizeof(double) * (size_t)n, fbytes = flags ? sizeof(int) * chol_flag_words(n) : 0;
-  char* xb = reinterpret_cast<char*>(x);
-  char* fb = reinterpret_cast<char*>(flags);
-  if (flags && fb >= xb + xbytes && fb - xb <= (ptrdiff_t)(xbytes + 4096)) {
-    (void)hipMemsetAsync(x, 0xFF, (size_t)(fb - xb) + fbytes, s);
+// The one host-side preset of a solve: the failure word to 0; x and the flags to 0xFF bytes ("nothing published yet";
+// one fill when the flags directly follow x, as in the BA workspace); the hand-over slots of the panel tiles likewise
+// (data-tagged: 0xFF bytes = not there yet).
+void launch_chol_preset(const CholSystem& c, hipStream_t s) {
+  (void)hipMemsetAsync(c.fail, 0, sizeof(int), s);
+  const size_t xbytes = sizeof(double) * (size_t)c.n, fbytes = sizeof(int) * chol_flag_words(c.n);
+  const char* xb = reinterpret_cast<const char*>(c.x);
+  const char* fb = reinterpret_cast<const char*>(c.flags);
+  if (fb >= xb + xbytes && fb - xb <= (ptrdiff_t)(xbytes + 4096)) {
+    (void)hipMemsetAsync(c.x, 0xFF, (size_t)(fb - xb) + fbytes, s);
   } else {
-    (void)hipMemsetAsync(x, 0xFF, xbytes, s);
-    if (flags) (void)hipMemsetAsync(flags, 0xFF, fbytes, s);
+    (void)hipMemsetAsync(c.x, 0xFF, xbytes, s);
+    (void)hipMemsetAsync(c.flags, 0xFF, fbytes, s);
   }
-  const bool single = launch_chol_factor(sys, n, ld, lm, ep, fail_flag, flags, ldiag, s);
-  launch_chol_backsolve(sys, n, ld, x, flags, ldiag, fail_flag, s, single);
+  (void)hipMemsetAsync(c.ldiag + chol_lfin_offset(c.n), 0xFF, sizeof(double) * chol_tiles(c.n) * NB * NB, s);
+}
+
+void launch_chol_solve(const CholSystem& c, double lm, double ep, hipStream_t s, bool preset_done) {
+  if (c.n <= 0) return;
+  if (!preset_done) launch_chol_preset(c, s);
+  const bool single = launch_chol_factor(c, lm, ep, s);
+  launch_chol_backsolve(c, single, s);
+}
+
+// droid_chol_solve's scratch buffer: the augmented system, then ldiag, then the flags
+size_t CholSystem::scratch_doubles(int n) {
+  if (n <= 0) return 0;
+  return (size_t)(n + 1) * chol_ld(n) + chol_ldiag_doubles(n) + (chol_flag_words(n) + 1) / 2 + 16;
+}
+CholSystem::CholSystem(double* scratch, int n_, double* x_, int* fail_)
+    : S(scratch), n(n_), ld(chol_ld(n_)), x(x_), fail(fail_) {
+  ldiag = S + (size_t)(n + 1) * ld;
+  flags = reinterpret_cast<int*>(ldiag + chol_ldiag_doubles(n));
 }
 
 #ifdef CHOL_STAMPS
