@@ -11,6 +11,7 @@
 
 #include "../../include/droid_backends_hip.h"
 #include "ba_internal.hpp"
+#include "graph.hpp"
 
 namespace droid {
 // corr.hip
@@ -552,6 +553,49 @@ int droid_depth_filter(const float* poses, const float* disps, const float* intr
   if (!poses || !disps || !intrinsics || !ix || !thresh || !counter) return fail(DROID_E_ARG, "depth_filter: null %s", "pointer");
   launch_depth_filter(poses, disps, intrinsics, ix, thresh, num, nbuf, H, W, counter, (hipStream_t)stream);
   return check_hip("depth_filter");
+}
+
+// ---------------------------------------------------------------------------- factor-graph edge selection
+// sizes every proximity entry point checks; <0 after fail()
+static int proximity_check(int t, int t0, int t1, int n_known, int cap) {
+  if (t < 0 || t0 < 0 || t1 < 0) return fail(DROID_E_ARG, "proximity_edges: negative %s", "t / t0 / t1");
+  if (t1 > t0) return fail(DROID_E_ARG, "proximity_edges: %s", "t1 > t0 (columns must start at or before the rows)");
+  if (n_known < 0 || cap < 0) return fail(DROID_E_ARG, "proximity_edges: negative %s", "n_known / cap");
+  if (t > t0 && (int64_t)(t - t0) * (t - t1) > PROX_MAX_CELLS)
+    return fail(DROID_E_ARG, "proximity_edges: %s", "rectangle above 1048576 cells (its suppression bitmap has to fit in LDS)");
+  return DROID_OK;
+}
+
+size_t droid_proximity_workspace_bytes(int t, int t0, int t1, int n_known, int cap) {
+  if (proximity_check(t, t0, t1, n_known, cap)) return 0;
+  return prox_workspace_bytes(t, t0, t1, n_known, cap);
+}
+
+int droid_proximity_edges(const float* dist, int ld, int bidirectional, int t, int t0, int t1, int rad, int nms,
+                          float thresh, int max_factors, int stereo, const int64_t* sup_ii, const int64_t* sup_jj,
+                          int n_sup, const int64_t* known_ii, const int64_t* known_jj, int n_known,
+                          int64_t* edges_out, int cap, int* count_out, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+  int rc = proximity_check(t, t0, t1, n_known, cap);
+  if (rc) return rc;
+  if (rad < 0) return fail(DROID_E_ARG, "proximity_edges: bad %s", "rad (< 0)");
+  if (nms < 0 || nms > 1024) return fail(DROID_E_ARG, "proximity_edges: bad %s", "nms (0 .. 1024)");
+  if (n_sup < 0) return fail(DROID_E_ARG, "proximity_edges: negative %s", "n_sup");
+  if (ld < t) return fail(DROID_E_ARG, "proximity_edges: %s", "row pitch of dist below t");
+  const int64_t bound = prox_edge_bound(t, t0, t1, rad, max_factors, stereo);
+  if (cap < bound) return fail(DROID_E_ARG, "proximity_edges: %s", "cap below max(forced edges, max_factors + 2)");
+  if (!count_out) return fail(DROID_E_ARG, "proximity_edges: null %s", "count_out");
+  if (t > t0) {
+    if (!dist || !workspace || (bound > 0 && !edges_out)) return fail(DROID_E_ARG, "proximity_edges: null %s", "dist / edges_out / workspace");
+    if ((n_sup > 0 && (!sup_ii || !sup_jj)) || (n_known > 0 && (!known_ii || !known_jj)))
+      return fail(DROID_E_ARG, "proximity_edges: null %s", "edge list");
+    if (workspace_bytes < prox_workspace_bytes(t, t0, t1, n_known, cap))
+      return fail(DROID_E_WORKSPACE, "proximity_edges: %s", "workspace too small");
+  }
+  ProxArgs a{dist, ld, bidirectional ? 1 : 0, t, t0, t1, rad, nms, thresh, max_factors, stereo ? 1 : 0, sup_ii, sup_jj, n_sup,
+             known_ii, known_jj, n_known, edges_out, cap, count_out, workspace};
+  launch_proximity_edges(a, (hipStream_t)stream);
+  return check_hip("proximity_edges");
 }
 
 }  // extern "C"

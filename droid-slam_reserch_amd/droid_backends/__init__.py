@@ -20,7 +20,8 @@ from ._lib import DroidBackendError  # noqa: F401
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
            "altcorr_backward", "corr_index_forward", "corr_index_backward",
            "altcorr_pyramid_forward", "reproject", "motion_features", "frame_distance_matrix",
-           "corr_pyramid_forward"]  # the last four are additions
+           "corr_pyramid_forward",  # the last four are additions
+           "proximity_edges"]       # add_proximity_factors' edge selection, on the device
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
 _workspaces = {}   # (device index, stream handle) -> _Workspace
@@ -218,6 +219,77 @@ def frame_distance_matrix(poses, disps, intrinsics, n, beta, bidirectional=True)
                                                int(H), int(W), float(beta), d.data_ptr(), _stream()),
                "frame_distance_matrix")
     return .5 * (d + d.t()) if bidirectional else d
+
+
+_prox_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of proximity_edges
+
+
+def _forced_before(i, m):
+    """sum over k < i of min(k, m): edges (i, j) step 4 emits for the frames before frame i."""
+    return i * (i - 1) // 2 if i <= m + 1 else m * (m + 1) // 2 + (i - 1 - m) * m
+
+
+def proximity_edge_bound(t, t0, t1, rad, max_factors, stereo):
+    """Most edges one selection can return (include/droid_backends_hip.h, droid_proximity_edges: `cap`)."""
+    if t <= t0:
+        return 0
+    forced = (t - t0 if stereo else 0) + 2 * (_forced_before(t, rad + 1) - _forced_before(t0, rad + 1))
+    return max(forced, min(max_factors + 2, forced + 2 * (t - t0) * (t - t1)))
+
+
+def proximity_edges(poses, disps, intrinsics, t, t0, t1, rad, nms, beta, thresh, max_factors, stereo,
+                    sup_ii, sup_jj, known_ii=None, known_jj=None, dist=None):
+    """The edges `FactorGraph.add_proximity_factors(t0, t1, rad, nms, beta, thresh)` adds
+    (droid_slam/factor_graph.py:315-379), selected on the device: returns (ii, jj), int64, in the reference's order.
+
+    t = frames in use (`video.counter.value`), max_factors / stereo = `graph.max_factors` / `video.stereo`;
+    sup_ii / sup_jj = the edges that suppress their neighbourhood (cat of active, bad and inactive edges);
+    known_ii / known_jj (optional) = active + inactive edges: with them the result is already what
+    `__filter_repeated_edges` (:44-55) would leave.  The frame-distance matrix is computed here with one
+    droid_frame_distance_matrix launch unless `dist` -- a DIRECTED [n, n] float32 matrix, n >= t, as that operator
+    writes it -- is given (then poses / disps / intrinsics are not looked at).  The contract, with the points where
+    it settles what the reference leaves open, is in include/droid_backends_hip.h.  One synchronisation: the edge
+    count is read back to size the result."""
+    lib = _lib.load()
+    t, t0, t1, rad, nms, max_factors = int(t), int(t0), int(t1), int(rad), int(nms), int(max_factors)
+    _check_index(sup_ii, "sup_ii")
+    _check_index(sup_jj, "sup_jj")
+    if (known_ii is None) != (known_jj is None):
+        raise RuntimeError("proximity_edges: known_ii and known_jj go together")
+    if known_ii is not None:
+        _check_index(known_ii, "known_ii")
+        _check_index(known_jj, "known_jj")
+    if dist is None:
+        for x, nm in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
+            _check_f32(x, nm)
+        dist = frame_distance_matrix(poses, disps, intrinsics, t, beta, bidirectional=False)
+    else:
+        if not dist.is_cuda:
+            raise RuntimeError("dist must be a HIP (cuda) tensor: droid_backends has no CPU path")
+        if dist.dtype != torch.float32 or dist.dim() != 2 or (dist.numel() and dist.stride(1) != 1):
+            raise RuntimeError("proximity_edges: dist must be a float32 matrix with unit column stride")
+        if dist.shape[0] < t or dist.shape[1] < t:
+            raise RuntimeError("proximity_edges: dist is smaller than [t, t]")
+    dev = dist.device
+    n_sup, n_known = int(sup_ii.shape[0]), 0 if known_ii is None else int(known_ii.shape[0])
+    if int(sup_jj.shape[0]) != n_sup or (n_known and int(known_jj.shape[0]) != n_known):
+        raise RuntimeError("proximity_edges: ii and jj of an edge list must have one length")
+    cap = proximity_edge_bound(t, t0, t1, rad, max_factors, bool(stereo))
+    nbytes = lib.droid_proximity_workspace_bytes(t, t0, t1, n_known, cap)
+    key = _ws_key(dev)
+    ws = _prox_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _prox_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+    out = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ld = int(dist.stride(0)) if dist.shape[0] > 1 else max(int(dist.shape[1]), t)
+    _lib.check(lib.droid_proximity_edges(
+        _ptr(dist) or None, ld, 1, t, t0, t1, rad, nms, float(thresh), max_factors, int(bool(stereo)),
+        _ptr(sup_ii) if n_sup else None, _ptr(sup_jj) if n_sup else None, n_sup,
+        _ptr(known_ii) if n_known else None, _ptr(known_jj) if n_known else None, n_known,
+        out.data_ptr() if cap else None, cap, count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "proximity_edges")
+    n = int(count.item())   # the one synchronisation (the reference's torch.as_tensor(es) is one too)
+    return out[:n, 0], out[:n, 1]
 
 
 def projmap(poses, disps, intrinsics, ii, jj):

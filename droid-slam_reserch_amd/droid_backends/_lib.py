@@ -24,6 +24,7 @@ SYMBOLS = [
     "droid_ba_solve_update", "droid_ba_profile_iteration", "droid_ba_system", "droid_ba_status",
     "droid_ba_attach_status_mirror", "droid_ba_attach_launch_hints", "droid_chol_solve", "droid_chol_scratch_doubles", "droid_reproject_motion",
     "droid_frame_distance", "droid_frame_distance_matrix", "droid_projmap", "droid_iproj", "droid_depth_filter",
+    "droid_proximity_workspace_bytes", "droid_proximity_edges",
 ]
 
 DROID_F16, DROID_F32, DROID_F64 = 0, 1, 2
@@ -87,8 +88,13 @@ def load() -> ctypes.CDLL:
     lib.droid_projmap.argtypes = [vp] * 5 + [c_int] * 4 + [vp, vp, vp]
     lib.droid_iproj.argtypes = [vp] * 3 + [c_int] * 3 + [vp, vp]
     lib.droid_depth_filter.argtypes = [vp] * 5 + [c_int] * 4 + [vp, vp]
+    lib.droid_proximity_workspace_bytes.argtypes = [c_int] * 5
+    lib.droid_proximity_workspace_bytes.restype = sz
+    lib.droid_proximity_edges.argtypes = ([vp] + [c_int] * 7 + [c_float, c_int, c_int, vp, vp, c_int, vp, vp, c_int,
+                                                                vp, c_int, vp, vp, sz, vp])
     for s in SYMBOLS[2:]:
-        if s not in ("droid_ba_workspace_bytes", "droid_ba_system", "droid_ba_packed_system", "droid_chol_scratch_doubles"):
+        if s not in ("droid_ba_workspace_bytes", "droid_ba_system", "droid_ba_packed_system", "droid_chol_scratch_doubles",
+                     "droid_proximity_workspace_bytes"):
             getattr(lib, s).restype = c_int
     if lib.droid_abi_version() != 1:
         raise DroidBackendError("ABI version mismatch")

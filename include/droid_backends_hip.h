@@ -287,6 +287,50 @@ int droid_depth_filter(const float *poses, const float *disps, const float *intr
                        const int64_t *ix, const float *thresh, int num, int nbuf, int H, int W,
                        float *counter, void *stream);
 
+/* ------------------------------------------------------------------ factor-graph edge selection */
+
+/* The edge list `FactorGraph.add_proximity_factors` (droid_slam/factor_graph.py:315-379) hands to `add_factors`,
+ * and the duplicate filter `add_factors` starts with (:44-55), selected on the stream from the frame-distance matrix
+ * and the edges the graph holds: no host round trip, 4 stream operations whatever t is and however many edges are
+ * accepted.  Not one of the reference's nine operators (the reference does this in a host loop with one blocking
+ * read per candidate).
+ *
+ * Rows of the candidate rectangle are frames [t0,t), columns frames [t1,t); t1 <= t0 (else DROID_E_ARG).
+ *  1. d[i,j] = 0.5f * (dist[i*ld+j] + dist[j*ld+i]) in fp32 when `bidirectional`, else dist[i*ld+j].  `dist` is the
+ *     directed matrix droid_frame_distance_matrix writes (ld >= t floats per row); it is only read.
+ *  2. d = inf where i - rad < j, and where d > 100.
+ *  3. Every suppressing edge (i,j) -- the caller passes active + bad + inactive edges -- puts d = inf on the cells
+ *     (i+di, j+dj) with |di| + |dj| <= max(min(|i-j| - 2, nms), 0) that lie in the rectangle.  Duplicates and edges
+ *     anywhere outside the rectangle are fine.
+ *  4. Forced edges, in this order: for i in [t0,t): (i,i) when `stereo`; then for j in [max(i-rad-1,0), i): (i,j),
+ *     (j,i).  Their cells become inf.
+ *  5. The cells in ascending d, ties by ascending flat index (i-t0)*(t-t1) + (j-t1) (the reference's argsort leaves
+ *     ties open): skip the cell when its d, as modified so far, is > thresh; STOP when the list already holds more
+ *     than max_factors edges; else append (i,j), (j,i) and put the diamond of step 3 around (i,j) to inf.
+ *     max_factors = -1 (the FactorGraph default) therefore yields the forced edges only.
+ *  6. When n_known > 0: every edge that is in the known list (active + inactive) is dropped, the order kept.
+ * edges_out [cap,2] int64 receives the edges, *count_out (device int) their number.  cap must be at least the most
+ * steps 4-5 can produce: max(forced, min(max_factors + 2, forced + 2 * cells)) with forced = the count of step 4,
+ * cells = (t-t0)*(t-t1).  t <= t0 gives an empty list.
+ *
+ * Where this differs from the reference's text:
+ *  - The reference addresses d by flat index, so in step 4 a column j < t1 lands in another row (or raises
+ *    IndexError).  Here a cell outside the rectangle is ignored.  For t1 < t0 and for t1 = t0 = 0 -- every call the
+ *    reference makes -- the cell it hits is at inf already and the lists are identical (swept in
+ *    tests/test_proximity_ref.py); t1 = t0 > 0 is legal here but outside that claim.
+ *  - A cell at inf or NaN is never selected, also not with thresh = inf (`inf > inf` is false in the reference).
+ *  - Limits: the suppression bitmap of the rectangle lives in LDS, so cells <= 1048576 (1024 x 1024), and
+ *    nms <= 1024; beyond either: DROID_E_ARG.  More than 16384 cells with d <= thresh take a slower sort (LDS sorts
+ *    of 16384 + merges by one workgroup); results are the same.
+ * Workspace: droid_proximity_workspace_bytes (host arithmetic; 0 for sizes droid_proximity_edges rejects).
+ * Concurrent calls need separate workspaces. */
+size_t droid_proximity_workspace_bytes(int t, int t0, int t1, int n_known, int cap);
+int droid_proximity_edges(const float *dist, int ld, int bidirectional, int t, int t0, int t1, int rad, int nms,
+                          float thresh, int max_factors, int stereo, const int64_t *sup_ii, const int64_t *sup_jj,
+                          int n_sup, const int64_t *known_ii, const int64_t *known_jj, int n_known,
+                          int64_t *edges_out, int cap, int *count_out, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif
