@@ -30,6 +30,10 @@ int launch_altcorr_forward(const void* f1, const void* f2, const float* coords, 
 int launch_altcorr_backward(const float* f1, const float* f2, const float* coords,
                             const float* corr_grad, float* f1g, float* f2g, int B, int N, int H1,
                             int W1, int H2, int W2, int C, int r, hipStream_t s);
+// corr_volume.hip
+int launch_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
+                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, int dtype,
+                               hipStream_t s);
 // geom.hip
 void launch_frame_distance(const float* poses, const float* disps, const float* intr,
                            const int64_t* ii, const int64_t* jj, int E, int nbuf, int H, int W,
@@ -124,6 +128,26 @@ int droid_corr_pyramid_forward(const void* const* volumes, const float* coords, 
   int rc = launch_corr_pyramid_forward(volumes, coords, corr, B, H1, W1, radius, levels, dtype, (hipStream_t)stream);
   if (rc) return fail(rc, "corr_pyramid_forward: %s", "unsupported configuration (radius 3 or 4, levels that divide the map)");
   return check_hip("corr_pyramid_forward");
+}
+
+int droid_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
+                              int nbuf, int ncam, int C, int H, int W, int levels, int64_t slot0, int64_t cap, int dtype,
+                              void* stream) {
+  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "dtype (f16 or f32)");
+  if (E < 0 || nbuf <= 0 || ncam < 1 || ncam > 2) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "E / nbuf / ncam");
+  if (C <= 0 || C % 32 != 0 || C > 256) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "C (a multiple of 32, at most 256)");
+  if (H < 8 || W < 8 || W % 8 != 0 || ((long long)H * W) % 16 != 0 || (long long)H * W > (1 << 24))
+    return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "map size (H, W >= 8, W % 8 == 0, H * W % 16 == 0)");
+  if (levels < 1 || levels > 4) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "levels (1 .. 4)");
+  if (slot0 < 0 || cap < 0 || slot0 + E > cap) return fail(DROID_E_ARG, "corr_volume_pyramid: %s", "slot0 + E exceeds cap");
+  if (E == 0) return DROID_OK;
+  if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pointer");
+  for (int l = 0; l < levels; l++)
+    if (!levels_out[l]) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pyramid level");
+  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, dtype,
+                                      (hipStream_t)stream);
+  if (rc) return fail(rc, "corr_volume_pyramid: %s", "unsupported configuration");
+  return check_hip("corr_volume_pyramid");
 }
 
 int droid_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,

@@ -21,7 +21,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "altcorr_backward", "corr_index_forward", "corr_index_backward",
            "altcorr_pyramid_forward", "reproject", "motion_features", "frame_distance_matrix",
            "corr_pyramid_forward",  # the last four are additions
-           "proximity_edges"]       # add_proximity_factors' edge selection, on the device
+           "proximity_edges",       # add_proximity_factors' edge selection, on the device
+           "corr_volume_pyramid"]   # CorrBlock.__init__ for a list of edges, in one launch
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
 _workspaces = {}   # (device index, stream handle) -> _Workspace
@@ -434,6 +435,53 @@ def corr_pyramid_forward(pyramid, coords, radius):
     _lib.check(lib.droid_corr_pyramid_forward(ptrs, coords.data_ptr(), corr.data_ptr(), B, H1, W1, r, len(levels),
                                               _corr_dtype(levels[0], "pyramid"), _stream()), "corr_pyramid_forward")
     return [corr]
+
+
+def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0):
+    """CorrBlock.__init__ (droid_slam/modules/corr.py:24-38, 63-71) for the edges ii -> jj in one launch, from the
+    feature buffer as DepthVideo holds it: fmaps [nbuf, ncam, C, h, w] (or [nbuf, C, h, w]) float16 / float32, channels
+    first; ii, jj [E] int64.  Edge e correlates fmaps[ii[e], 0] / 4 with fmaps[jj[e], c] / 4, c = 1 for a stereo edge
+    (ncam == 2 and ii[e] == jj[e]), and pools level l+1 from the rounded level l like avg_pool2d; an index outside
+    [0, nbuf) yields zeros.  Returns the list CorrBlock.corr_pyramid: level l = [E, h, w, h>>l, w>>l] of fmaps' dtype.
+    With `out` (a list of capacity tensors [cap, h, w, h>>l, w>>l]) the edges are written to slots
+    [offset, offset + E) -- every other slot is left as it is -- and views of those slots are returned: allocate the
+    pyramid once and build new edges at offset = number of edges held, instead of CorrBlock.cat.
+    The contract is in include/droid_backends_hip.h (droid_corr_volume_pyramid).  An addition."""
+    lib = _lib.load()
+    _check_input(fmaps, "fmaps")
+    _check_index(ii, "ii")
+    _check_index(jj, "jj")
+    if fmaps.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"corr_volume_pyramid: fmaps must be float16 or float32, got {fmaps.dtype}")
+    if fmaps.dim() == 4:
+        fmaps = fmaps[:, None]
+    if fmaps.dim() != 5:
+        raise RuntimeError("corr_volume_pyramid: fmaps must be [nbuf, ncam, C, h, w] or [nbuf, C, h, w]")
+    nbuf, ncam, C, h, w = (int(x) for x in fmaps.shape)
+    levels, offset = int(levels), int(offset)
+    if ii.dim() != 1 or ii.shape != jj.shape:
+        raise RuntimeError("corr_volume_pyramid: ii and jj must be [E]")
+    E = int(ii.shape[0])
+    shapes = [(h, w, h >> l, w >> l) for l in range(levels)]
+    if out is None:
+        if offset != 0:
+            raise RuntimeError("corr_volume_pyramid: offset needs out")
+        out = [torch.empty((E,) + s, dtype=fmaps.dtype, device=fmaps.device) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) != levels:
+            raise RuntimeError(f"corr_volume_pyramid: out must hold {levels} levels")
+        for l, o in enumerate(out):
+            _check_input(o, f"out[{l}]")
+            if o.dtype != fmaps.dtype or o.dim() != 5 or tuple(o.shape[1:]) != shapes[l] or o.shape[0] != out[0].shape[0]:
+                raise RuntimeError(f"corr_volume_pyramid: out[{l}] must be [cap,{h},{w},{h >> l},{w >> l}] of {fmaps.dtype}")
+    cap = int(out[0].shape[0]) if levels > 0 else 0
+    if offset < 0 or offset + E > cap:
+        raise RuntimeError(f"corr_volume_pyramid: slots [{offset}, {offset + E}) do not fit the capacity {cap}")
+    ptrs = (ctypes.c_void_p * max(levels, 1))(*[o.data_ptr() for o in out])
+    _lib.check(lib.droid_corr_volume_pyramid(fmaps.data_ptr(), ii.data_ptr(), jj.data_ptr(), ptrs, E, nbuf, ncam, C, h,
+                                             w, levels, offset, cap, _DT[fmaps.dtype], _stream()), "corr_volume_pyramid")
+    return [o[offset:offset + E] for o in out]
 
 
 def corr_index_backward(volume, coords, corr_grad, radius):

@@ -59,6 +59,24 @@ int droid_corr_index_forward(const void *volume, const float *coords, void *corr
 int droid_corr_pyramid_forward(const void *const *volumes, const float *coords, void *corr, int B, int H1,
                                int W1, int radius, int levels, int dtype, void *stream);
 
+/* CorrBlock.__init__ for a list of edges in one launch (droid_slam/modules/corr.py:24-38, 63-71, as factor_graph.py:
+ * 112-117 calls it), from the feature buffer as DepthVideo holds it.  Not one of the reference's nine operators.
+ * fmaps [nbuf, ncam, C, H, W] dtype T (f16 or f32), channels first, ncam 1 or 2 ; ii, jj [E] int64.
+ * Edge e: A = fmaps[ii[e], 0], B = fmaps[jj[e], c], c = 1 when ncam == 2 and ii[e] == jj[e], else 0 (with ncam == 1
+ * the reference raises on ii == jj; here camera 0 is used).  a = T(A / 4), b = T(B / 4), rounded to T first;
+ *   level 0:   vol[e, p, q] = T(sum_c a[c, p] * b[c, q]), p, q flat pixel indices, products and sum in fp32;
+ *   level l+1: T(fp32(((v00 + v01) + v10) + v11) * 0.25f) of the ROUNDED level l over the (H2, W2) plane, size
+ *              (H >> (l+1), W >> (l+1)) -- avg_pool2d(., 2, stride=2) on dtype T bit for bit, odd sizes floor.
+ * levels_out: HOST array of `levels` (1..4) device pointers, level l = [cap, H, W, H>>l, W>>l] of T
+ * (CorrBlock.corr_pyramid[l], what droid_corr_pyramid_forward takes).  Edge e is written to slot slot0 + e, completely;
+ * no other slot is touched (slot0 + E <= cap).  An edge with ii or jj outside [0, nbuf) yields zeros.  No atomics: the
+ * same bits on every run, and an edge's bits do not depend on E or on its slot.
+ * C % 32 == 0, C <= 256 ; H, W >= 8, W % 8 == 0, H * W % 16 == 0 ; anything else returns DROID_E_ARG with a message
+ * (there is no fallback).  All argument checks are host-side and precede any HIP call; E == 0 launches nothing. */
+int droid_corr_volume_pyramid(const void *fmaps, const int64_t *ii, const int64_t *jj, void *const *levels_out,
+                              int E, int nbuf, int ncam, int C, int H, int W, int levels, int64_t slot0,
+                              int64_t cap, int dtype, void *stream);
+
 /* corr_index_backward (droid.cpp:180-191 -> correlation_kernels.cu:157-185).
  * corr_grad [B,2r+1,2r+1,H1,W1] dtype ; volume_grad [B,H1,W1,H2,W2] dtype (written completely). */
 int droid_corr_index_backward(const float *coords, const void *corr_grad, void *volume_grad, int B,
