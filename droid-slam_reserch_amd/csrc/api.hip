@@ -19,6 +19,8 @@ int launch_corr_index_forward(const void* volume, const float* coords, void* cor
                               int W1, int H2, int W2, int r, int dtype, hipStream_t s);
 int launch_corr_pyramid_forward(const void* const* volumes, const float* coords, void* corr, int B, int H1, int W1,
                                 int r, int levels, int dtype, hipStream_t s);
+int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                                      void* corr, int B, int H1, int W1, int r, int levels, int dtype, hipStream_t s);
 int launch_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
                                int H1, int W1, int H2, int W2, int r, int dtype, hipStream_t s);
 int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t* ii, const int64_t* jj,
@@ -32,8 +34,8 @@ int launch_altcorr_backward(const float* f1, const float* f2, const float* coord
                             int W1, int H2, int W2, int C, int r, hipStream_t s);
 // corr_volume.hip
 int launch_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
-                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, int dtype,
-                               hipStream_t s);
+                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, const int64_t* slots,
+                               long long cap, int dtype, hipStream_t s);
 // geom.hip
 void launch_frame_distance(const float* poses, const float* disps, const float* intr,
                            const int64_t* ii, const int64_t* jj, int E, int nbuf, int H, int W,
@@ -144,10 +146,51 @@ int droid_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_
   if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pointer");
   for (int l = 0; l < levels; l++)
     if (!levels_out[l]) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pyramid level");
-  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, dtype,
-                                      (hipStream_t)stream);
+  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, nullptr,
+                                      (long long)cap, dtype, (hipStream_t)stream);
   if (rc) return fail(rc, "corr_volume_pyramid: %s", "unsupported configuration");
   return check_hip("corr_volume_pyramid");
+}
+
+int droid_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, const float* coords, void* corr,
+                                     int B, int64_t cap, int H1, int W1, int radius, int levels, int dtype, void* stream) {
+  if (B < 0 || B > 65535 || H1 <= 0 || W1 <= 0) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "shape");
+  if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "dtype");
+  if (radius != 3 && radius != 4) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "radius (3 or 4)");
+  if (levels < 1 || levels > 8 || (H1 >> (levels - 1)) < 1 || (W1 >> (levels - 1)) < 1)
+    return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "levels (1 .. 8, each at least one pixel)");
+  if (cap < 1) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "cap (at least 1)");
+  if (B == 0) return DROID_OK;
+  if (!slots) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "slots");
+  if (!volumes || !coords || !corr) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "pointer");
+  for (int l = 0; l < levels; l++)
+    if (!volumes[l]) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "pyramid level");
+  int rc = launch_corr_pyramid_forward_slots(volumes, slots, (long long)cap, coords, corr, B, H1, W1, radius, levels, dtype,
+                                             (hipStream_t)stream);
+  if (rc) return fail(rc, "corr_pyramid_forward_slots: %s", "unsupported configuration");
+  return check_hip("corr_pyramid_forward_slots");
+}
+
+int droid_corr_volume_pyramid_slots(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out,
+                                    const int64_t* slots, int E, int nbuf, int ncam, int C, int H, int W, int levels,
+                                    int64_t cap, int dtype, void* stream) {
+  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "dtype (f16 or f32)");
+  if (E < 0 || nbuf <= 0 || ncam < 1 || ncam > 2) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "E / nbuf / ncam");
+  if (C <= 0 || C % 32 != 0 || C > 256)
+    return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "C (a multiple of 32, at most 256)");
+  if (H < 8 || W < 8 || W % 8 != 0 || ((long long)H * W) % 16 != 0 || (long long)H * W > (1 << 24))
+    return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "map size (H, W >= 8, W % 8 == 0, H * W % 16 == 0)");
+  if (levels < 1 || levels > 4) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "levels (1 .. 4)");
+  if (cap < 1) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "cap (at least 1)");
+  if (E == 0) return DROID_OK;
+  if (!slots) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "slots");
+  if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "pointer");
+  for (int l = 0; l < levels; l++)
+    if (!levels_out[l]) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "pyramid level");
+  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, 0, slots, (long long)cap,
+                                      dtype, (hipStream_t)stream);
+  if (rc) return fail(rc, "corr_volume_pyramid_slots: %s", "unsupported configuration");
+  return check_hip("corr_volume_pyramid_slots");
 }
 
 int droid_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,

@@ -140,6 +140,20 @@ struct Combine<__half, R> {
   }
 };
 
+// ---- slot indirection (droid_corr_pyramid_forward_slots) ----------------------------------------------------
+// Batch entry b reads the planes of slot slots[b] of a capacity buffer; its coordinates and its output stay at b.  b is
+// blockIdx.y, so the slot is one scalar load per workgroup.  SLOTTED = false instantiates exactly the identity addressing
+// (slot = b) without the load and the range check.  A slot outside [0, cap) gives zeros, like an edge index outside the
+// frame buffer in corr_volume_pyramid and altcorr_pyramid_forward -- WITHOUT a branch: the entry runs on slot 0 with no
+// tap taken and all four weights zero (0 * 0, summed: +0 in every element type, whatever the coordinates are).  A branch
+// on the slot in front of the coordinate loads would put the two memory latencies in series in every workgroup.
+__device__ __forceinline__ bool slot_of(const int64_t* __restrict__ slots, int b, long long cap, size_t* slot) {
+  const long long s = slots[b];
+  const bool live = s >= 0 && s < cap;
+  *slot = live ? (size_t)s : 0;
+  return live;
+}
+
 // ---- corr_index_forward ------------------------------------------------------------------
 // One thread per query pixel, 64 consecutive pixels per wave: each of the (2r+1)^2 output planes
 // is written as 64 consecutive elements.  A query's window is (2r+2) rows of (2r+2) contiguous
@@ -197,12 +211,13 @@ struct RowLoad<double, NT> {
 // out_bstride: elements between the outputs of consecutive batch entries ((2r+1)^2 H1W1 for the reference's operator;
 // levels (2r+1)^2 H1W1 when the levels of a pyramid are written side by side, corr_pyramid_forward); cscale: the
 // coordinates are multiplied by it first (1, or 2^-level: exact).
-template <typename T, int R>
+template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(const T* __restrict__ volume,
                                                                  const float* __restrict__ coords,
                                                                  T* __restrict__ corr, int H1W1,
                                                                  int H2, int W2, size_t vol_elems,
-                                                                 size_t out_bstride, float cscale) {
+                                                                 size_t out_bstride, float cscale,
+                                                                 const int64_t* __restrict__ slots, long long cap) {
   typedef typename Elem<T>::work work;
   constexpr int RD = 2 * R + 1, NT = RD + 1;
   const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -210,12 +225,15 @@ __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(con
   if (pix >= H1W1) return;
   const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale;
   const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale;
+  size_t slot = (size_t)b;
+  bool live = true;
+  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
   const Bilin bl = bilin_setup(x0, y0, R);
-  const T* plane = volume + ((size_t)b * H1W1 + pix) * ((size_t)H2 * W2);
+  const T* plane = volume + (slot * H1W1 + pix) * ((size_t)H2 * W2);
   const uintptr_t vbeg = reinterpret_cast<uintptr_t>(volume);
   const uintptr_t vend = vbeg + vol_elems * sizeof(T);
   // any tap of the window inside the plane at all?
-  const bool xany = (bl.x1 + NT > 0) && (bl.x1 < W2);
+  const bool xany = live && (bl.x1 + NT > 0) && (bl.x1 < W2);
 
   work tap[NT][NT];  // [row j (y)][col i (x)]
 #pragma unroll
@@ -248,10 +266,11 @@ __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(con
   }
   const float one = 1.0f;
   // weights rounded to the element type (ck:55-65)
-  const work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )
-  const work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  const work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  const work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )
+  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
+  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
+  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
   T* out = corr + (size_t)b * out_bstride + pix;
   Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
 }
@@ -266,11 +285,12 @@ constexpr int CS_MAXPLANE = 192;  // bytes per plane served by this kernel.  Mea
                                   // (fp16 level 3) 37.6 -> 35.6 us, 192-byte planes (fp32 level 3) 39.2 -> 27.4 us; 384- and 768-byte
                                   // planes (level 2) get SLOWER this way (88 -> 150 us, 64 -> 212 us: 25-49 KB of LDS per wave leave
                                   // 3-6 waves per CU and nothing overlaps the load -> barrier -> gather sequence), so they keep the row loads
-template <typename T, int R>
+template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restrict__ volume,
                                                                const float* __restrict__ coords,
                                                                T* __restrict__ corr, int H1W1, int H2, int W2,
-                                                               size_t out_bstride, float cscale) {
+                                                               size_t out_bstride, float cscale,
+                                                               const int64_t* __restrict__ slots, long long cap) {
   typedef typename Elem<T>::work work;
   constexpr int RD = 2 * R + 1, NT = RD + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -279,7 +299,10 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
   const int nq = min(64, H1W1 - pix0);
   const int PB = H2 * W2 * (int)sizeof(T);      // bytes per plane: a multiple of 16 (checked by the launcher)
   const int pitch = PB + 4;
-  const unsigned char* src = reinterpret_cast<const unsigned char*>(volume + ((size_t)b * H1W1 + pix0) * ((size_t)H2 * W2));
+  size_t slot = (size_t)b;
+  bool live = true;
+  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(volume + (slot * H1W1 + pix0) * ((size_t)H2 * W2));
   const int nvec = (nq * PB) >> 4;
   for (int u = lane; u < nvec; u += 64) {
     const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)u * 16);
@@ -298,7 +321,7 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
 #pragma unroll
   for (int j = 0; j < NT; j++) {
     const int y1 = bl.y1 + j;
-    const bool rowok = (y1 >= 0) && (y1 < H2);
+    const bool rowok = live && (y1 >= 0) && (y1 < H2);
 #pragma unroll
     for (int i = 0; i < NT; i++) {
       const int x1 = bl.x1 + i;
@@ -307,21 +330,22 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
     }
   }
   const float one = 1.0f;
-  const work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
-  const work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  const work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  const work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
+  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
+  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
+  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
   T* out = corr + (size_t)b * out_bstride + pix;
   Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
 }
 
-template <typename T, int R>
+template <typename T, int R, bool SLOTTED>
 static bool launch_corr_small(const T* v, const float* coords, T* c, int B, int HW, int H2, int W2, size_t obs,
-                              float cs, hipStream_t s) {
+                              float cs, const int64_t* slots, long long cap, hipStream_t s) {
   const int PB = H2 * W2 * (int)sizeof(T);
   if (PB > CS_MAXPLANE || (PB & 15) != 0 || (reinterpret_cast<uintptr_t>(v) & 15) != 0) return false;
-  hipLaunchKernelGGL((corr_index_forward_small<T, R>), dim3((HW + 63) / 64, B), dim3(64), 64 * (PB + 4), s, v, coords, c,
-                     HW, H2, W2, obs, cs);
+  hipLaunchKernelGGL((corr_index_forward_small<T, R, SLOTTED>), dim3((HW + 63) / 64, B), dim3(64), 64 * (PB + 4), s, v,
+                     coords, c, HW, H2, W2, obs, cs, slots, cap);
   return true;
 }
 
@@ -337,11 +361,12 @@ template <typename T, int NT> struct RowWords;   // dwords a row load brings (Ro
 template <int NT> struct RowWords<__half, NT> { static constexpr int NW = RowLoad<__half, NT>::NW; };
 template <int NT> struct RowWords<float, NT> { static constexpr int NW = NT; };
 
-template <typename T, int R>
+template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restrict__ volume,
                                                                const float* __restrict__ coords,
                                                                T* __restrict__ corr, int H1W1, int H2, int W2,
-                                                               size_t vol_elems, size_t out_bstride, float cscale) {
+                                                               size_t vol_elems, size_t out_bstride, float cscale,
+                                                               const int64_t* __restrict__ slots, long long cap) {
   typedef typename Elem<T>::work work;
   constexpr int RD = 2 * R + 1, NT = RD + 1;
   static_assert(NT == 8, "eight window rows <-> eight lanes per query");
@@ -360,11 +385,14 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
   const int cpix = valid ? pix : H1W1 - 1;
   const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + cpix] * cscale;
   const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + cpix] * cscale;
+  size_t slot = (size_t)b;
+  bool live = true;
+  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
   const Bilin bl = bilin_setup(x0, y0, R);
   const uintptr_t vbeg = reinterpret_cast<uintptr_t>(volume);
   const uintptr_t vend = vbeg + vol_elems * sizeof(T);
   const size_t plane_elems = (size_t)H2 * W2;
-  const bool xany = valid && (bl.x1 + NT > 0) && (bl.x1 < W2);
+  const bool xany = valid && live && (bl.x1 + NT > 0) && (bl.x1 < W2);
   // ---- cooperative loads: pass `it` serves queries 8 it .. 8 it + 7
   const int lq = lane >> 3, lj = lane & 7;
 #pragma unroll
@@ -374,7 +402,7 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
     const bool qany = __shfl((int)xany, q) != 0;
     const int y1 = qy1 + lj;
     if (qany && y1 >= 0 && y1 < H2) {
-      const T* rp = volume + ((size_t)b * H1W1 + (pix0 + q)) * plane_elems + (ptrdiff_t)y1 * W2 + qx1;
+      const T* rp = volume + (slot * H1W1 + (pix0 + q)) * plane_elems + (ptrdiff_t)y1 * W2 + qx1;
       const uintptr_t a0 = reinterpret_cast<uintptr_t>(rp) & ~uintptr_t(3);
       if (a0 >= vbeg && a0 + NW * 4 <= vend) {   // (rows at the two ends of the tensor: the owner loads them itself)
         const u32a4* src = reinterpret_cast<const u32a4*>(a0);
@@ -401,7 +429,7 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
   __builtin_amdgcn_wave_barrier();
   if (!valid) return;
   // ---- the owner of the query collects its window
-  const T* plane = volume + ((size_t)b * H1W1 + pix) * plane_elems;
+  const T* plane = volume + (slot * H1W1 + pix) * plane_elems;
   work tap[NT][NT];  // [row j (y)][col i (x)]
 #pragma unroll
   for (int j = 0; j < NT; j++) {
@@ -445,24 +473,25 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
     }
   }
   const float one = 1.0f;
-  const work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
-  const work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  const work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  const work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
+  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
+  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
+  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
   T* out = corr + (size_t)b * out_bstride + pix;
   Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
 }
 
 // rows of at most 64 bytes (two or more window rows per 128-byte line), radius 3, half / float
-template <typename T, int R>
+template <typename T, int R, bool SLOTTED>
 static bool launch_corr_coop(const T* v, const float* coords, T* c, int B, int HW, int H2, int W2, size_t vol_elems,
-                             size_t obs, float cs, hipStream_t s) {
+                             size_t obs, float cs, const int64_t* slots, long long cap, hipStream_t s) {
   if constexpr (R != 3 || sizeof(T) > 4) {
     return false;
   } else {
     if (W2 * (int)sizeof(T) > 64 || (HW & 63) != 0) return false;
-    hipLaunchKernelGGL((corr_index_forward_coop<T, R>), dim3((HW + 255) / 256, B), dim3(256), 0, s, v, coords, c, HW, H2, W2,
-                       vol_elems, obs, cs);
+    hipLaunchKernelGGL((corr_index_forward_coop<T, R, SLOTTED>), dim3((HW + 255) / 256, B), dim3(256), 0, s, v, coords, c,
+                       HW, H2, W2, vol_elems, obs, cs, slots, cap);
     return true;
   }
 }
@@ -510,13 +539,16 @@ static int corr_index_forward_t(const void* volume, const float* coords, void* c
   T* c = static_cast<T*>(corr);
   const size_t vol_elems = (size_t)B * HW * H2 * W2;
   const size_t obs = (size_t)(2 * r + 1) * (2 * r + 1) * HW;
-  if (r == 3 && launch_corr_small<T, 3>(v, coords, c, B, HW, H2, W2, obs, 1.0f, s)) return 0;
-  if (r == 4 && launch_corr_small<T, 4>(v, coords, c, B, HW, H2, W2, obs, 1.0f, s)) return 0;
-  if (r == 3 && launch_corr_coop<T, 3>(v, coords, c, B, HW, H2, W2, vol_elems, obs, 1.0f, s)) return 0;
+  const int64_t* const ident = nullptr;   // slot = batch index
+  if (r == 3 && launch_corr_small<T, 3, false>(v, coords, c, B, HW, H2, W2, obs, 1.0f, ident, 0, s)) return 0;
+  if (r == 4 && launch_corr_small<T, 4, false>(v, coords, c, B, HW, H2, W2, obs, 1.0f, ident, 0, s)) return 0;
+  if (r == 3 && launch_corr_coop<T, 3, false>(v, coords, c, B, HW, H2, W2, vol_elems, obs, 1.0f, ident, 0, s)) return 0;
   if (r == 3)
-    hipLaunchKernelGGL((corr_index_forward_kernel<T, 3>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs, 1.0f);
+    hipLaunchKernelGGL((corr_index_forward_kernel<T, 3, false>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs,
+                       1.0f, ident, 0LL);
   else if (r == 4)
-    hipLaunchKernelGGL((corr_index_forward_kernel<T, 4>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs, 1.0f);
+    hipLaunchKernelGGL((corr_index_forward_kernel<T, 4, false>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs,
+                       1.0f, ident, 0LL);
   else
     hipLaunchKernelGGL((corr_index_forward_generic<T>), grid, block, 0, s, v, coords, c, HW, H2, W2, r);
   return 0;
@@ -537,9 +569,11 @@ int launch_corr_index_forward(const void* volume, const float* coords, void* cor
 // ([B,H1,W1,H1>>l,W1>>l]) at coords * 2^-l and writes channels [l (2r+1)^2, (l+1) (2r+1)^2) of
 // corr [B, levels (2r+1)^2, H1, W1] -- the tensor torch.cat(out_pyramid, dim=2) would build, without the cat
 // (600 MB of extra traffic at 256 edges) and without the per-level coordinate tensors.  One launch per level.
-template <typename T>
-static int corr_pyramid_forward_t(const void* const* volumes, const float* coords, void* corr, int B, int H1, int W1,
-                                  int r, int levels, hipStream_t s) {
+// SLOTTED: volumes[l] is a capacity buffer [cap, H1, W1, H1>>l, W1>>l] and batch entry b reads slot slots[b] of it
+// (droid_corr_pyramid_forward_slots); the whole-tensor guards of the row loads then span all cap slots.
+template <typename T, bool SLOTTED>
+static int corr_pyramid_forward_t(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                                  void* corr, int B, int H1, int W1, int r, int levels, hipStream_t s) {
   const int HW = H1 * W1, rd2 = (2 * r + 1) * (2 * r + 1);
   dim3 grid((HW + 255) / 256, B), block(256);
   const size_t obs = (size_t)levels * rd2 * HW;
@@ -547,27 +581,44 @@ static int corr_pyramid_forward_t(const void* const* volumes, const float* coord
     const int H2 = H1 >> l, W2 = W1 >> l;
     const T* v = static_cast<const T*>(volumes[l]);
     T* c = static_cast<T*>(corr) + (size_t)l * rd2 * HW;
-    const size_t vol_elems = (size_t)B * HW * H2 * W2;
+    const size_t vol_elems = (size_t)(SLOTTED ? cap : (long long)B) * HW * H2 * W2;
     const float cs = 1.0f / (float)(1 << l);
-    if (r == 3 && launch_corr_small<T, 3>(v, coords, c, B, HW, H2, W2, obs, cs, s)) continue;
-    if (r == 4 && launch_corr_small<T, 4>(v, coords, c, B, HW, H2, W2, obs, cs, s)) continue;
-    if (r == 3 && launch_corr_coop<T, 3>(v, coords, c, B, HW, H2, W2, vol_elems, obs, cs, s)) continue;
+    if (r == 3 && launch_corr_small<T, 3, SLOTTED>(v, coords, c, B, HW, H2, W2, obs, cs, slots, cap, s)) continue;
+    if (r == 4 && launch_corr_small<T, 4, SLOTTED>(v, coords, c, B, HW, H2, W2, obs, cs, slots, cap, s)) continue;
+    if (r == 3 && launch_corr_coop<T, 3, SLOTTED>(v, coords, c, B, HW, H2, W2, vol_elems, obs, cs, slots, cap, s)) continue;
     if (r == 3)
-      hipLaunchKernelGGL((corr_index_forward_kernel<T, 3>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs, cs);
+      hipLaunchKernelGGL((corr_index_forward_kernel<T, 3, SLOTTED>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems,
+                         obs, cs, slots, cap);
     else
-      hipLaunchKernelGGL((corr_index_forward_kernel<T, 4>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs, cs);
+      hipLaunchKernelGGL((corr_index_forward_kernel<T, 4, SLOTTED>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems,
+                         obs, cs, slots, cap);
   }
   return 0;
 }
 
+static bool corr_pyramid_shape_ok(int B, int H1, int W1, int r, int levels) {
+  return B <= 65535 && (r == 3 || r == 4) && levels >= 1 && levels <= 8 && (H1 >> (levels - 1)) >= 1 &&
+         (W1 >> (levels - 1)) >= 1;
+}
+
 int launch_corr_pyramid_forward(const void* const* volumes, const float* coords, void* corr, int B, int H1, int W1,
                                 int r, int levels, int dtype, hipStream_t s) {
-  if (B > 65535 || (r != 3 && r != 4) || levels < 1 || levels > 8 || (H1 >> (levels - 1)) < 1 || (W1 >> (levels - 1)) < 1)
-    return DROID_E_ARG;
+  if (!corr_pyramid_shape_ok(B, H1, W1, r, levels)) return DROID_E_ARG;
   switch (dtype) {
-    case DROID_F16: return corr_pyramid_forward_t<__half>(volumes, coords, corr, B, H1, W1, r, levels, s);
-    case DROID_F32: return corr_pyramid_forward_t<float>(volumes, coords, corr, B, H1, W1, r, levels, s);
-    case DROID_F64: return corr_pyramid_forward_t<double>(volumes, coords, corr, B, H1, W1, r, levels, s);
+    case DROID_F16: return corr_pyramid_forward_t<__half, false>(volumes, nullptr, 0, coords, corr, B, H1, W1, r, levels, s);
+    case DROID_F32: return corr_pyramid_forward_t<float, false>(volumes, nullptr, 0, coords, corr, B, H1, W1, r, levels, s);
+    case DROID_F64: return corr_pyramid_forward_t<double, false>(volumes, nullptr, 0, coords, corr, B, H1, W1, r, levels, s);
+  }
+  return DROID_E_ARG;
+}
+
+int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                                      void* corr, int B, int H1, int W1, int r, int levels, int dtype, hipStream_t s) {
+  if (!corr_pyramid_shape_ok(B, H1, W1, r, levels) || !slots || cap < 1) return DROID_E_ARG;
+  switch (dtype) {
+    case DROID_F16: return corr_pyramid_forward_t<__half, true>(volumes, slots, cap, coords, corr, B, H1, W1, r, levels, s);
+    case DROID_F32: return corr_pyramid_forward_t<float, true>(volumes, slots, cap, coords, corr, B, H1, W1, r, levels, s);
+    case DROID_F64: return corr_pyramid_forward_t<double, true>(volumes, slots, cap, coords, corr, B, H1, W1, r, levels, s);
   }
   return DROID_E_ARG;
 }

@@ -17,6 +17,7 @@
 //      there in 16-byte pieces (a whole 8 x w run per p when w <= 64), and one thread per (p, 8x8 block) pools
 //      levels 1-3 in registers from the rounded values.  Level 0 never comes back from memory.
 // a (P pixels x C) is transposed into LDS once per workgroup.  No atomics; an edge's bits do not depend on E or slot.
+// The slot of edge e is slot0 + e, or slots[e] when a slot list is given (droid_corr_volume_pyramid_slots).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,7 +35,9 @@ struct CvArgs {
   const int64_t* jj;
   void* out[4];
   int E, nbuf, ncam, C, H, W, levels;
-  long long slot0;
+  long long slot0;        // edge e -> slot slot0 + e, or
+  const int64_t* slots;   // (not null) -> slot slots[e]; outside [0, cap) the edge is skipped
+  long long cap;
   int nptiles, nbands, nxc;
 };
 
@@ -80,7 +83,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void corr_volume_pyram
   const T* fa = (const T*)a.fmaps + (valid ? (size_t)fi * a.ncam * C * hw : 0);
   const T* fb = (const T*)a.fmaps + (valid ? ((size_t)fj * a.ncam + cam) * C * hw : 0);
   const int p0 = pt * P;
-  const size_t slot = (size_t)(a.slot0 + e);
+  long long eslot = a.slot0 + e;
+  if (a.slots) {   // uniform over the workgroup (one scalar load): a skipped edge leaves before any barrier
+    eslot = a.slots[e];
+    if (eslot < 0 || eslot >= a.cap) return;
+  }
+  const size_t slot = (size_t)eslot;
   const T quarter = (T)0.25f;
 
   // a: [c][p] in memory -> [p][c], scaled.  T(x * 0.25) is the correctly rounded x / 4 (subnormal results included).
@@ -278,14 +286,16 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void corr_volume_pyram
 
 // Shapes the kernel takes (checked by the C entry point before any HIP call): C % 32 == 0, C <= 256, h, w >= 8,
 // w % 8 == 0, h * w % 16 == 0, levels 1..4.
+// slots == nullptr: edge e goes to slot slot0 + e; else to slots[e] of the cap slots (checked on the device).
 int launch_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
-                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, int dtype,
-                               hipStream_t s) {
+                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, const int64_t* slots,
+                               long long cap, int dtype, hipStream_t s) {
   if (dtype != DROID_F16 && dtype != DROID_F32) return DROID_E_ARG;
   CvArgs a{};
   a.fmaps = fmaps; a.ii = ii; a.jj = jj;
   for (int l = 0; l < levels; l++) a.out[l] = levels_out[l];
   a.E = E; a.nbuf = nbuf; a.ncam = ncam; a.C = C; a.H = H; a.W = W; a.levels = levels; a.slot0 = slot0;
+  a.slots = slots; a.cap = cap;
   const int P = dtype == DROID_F16 ? CvCfg<_Float16>::P : CvCfg<float>::P;
   const long long hw = (long long)H * W;
   a.nptiles = (int)((hw + P - 1) / P);

@@ -23,6 +23,7 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "corr_pyramid_forward",  # the last four are additions
            "proximity_edges",       # add_proximity_factors' edge selection, on the device
            "corr_volume_pyramid"]   # CorrBlock.__init__ for a list of edges, in one launch
+# droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
 _workspaces = {}   # (device index, stream handle) -> _Workspace
@@ -410,11 +411,14 @@ def corr_index_forward(volume, coords, radius):
     return [corr]
 
 
-def corr_pyramid_forward(pyramid, coords, radius):
+def corr_pyramid_forward(pyramid, coords, radius, slots=None):
     """CorrBlock.__call__ (droid_slam/modules/corr.py:40-50) without the torch.cat: pyramid = CorrBlock.corr_pyramid
     (list of [B,h,w,h>>l,w>>l] volumes of one dtype), coords [B,2,h,w] float32 at level-0 scale (the tensor __call__
     builds at :43-44).  Returns [corr] with corr [B, levels*(2r+1)^2, h, w] = torch.cat([corr_index_forward(
-    pyramid[l], coords / 2**l, r).view(B, -1, h, w) for l], dim=1), bit for bit.  An addition."""
+    pyramid[l], coords / 2**l, r).view(B, -1, h, w) for l], dim=1), bit for bit.  An addition.
+    With `slots` ([B] int64 on the device) the pyramid is a list of capacity buffers [cap,h,w,h>>l,w>>l] and entry b
+    reads slot slots[b]: the result of corr_pyramid_forward([p[slots] for p in pyramid], coords, radius) bit for bit,
+    without the gathered copy; a slot outside [0, cap) gives zeros for that entry (droid_corr_pyramid_forward_slots)."""
     lib = _lib.load()
     levels = list(pyramid)
     for i, p in enumerate(levels):
@@ -422,22 +426,33 @@ def corr_pyramid_forward(pyramid, coords, radius):
         if p.dtype != levels[0].dtype:
             raise RuntimeError("corr_pyramid_forward: pyramid levels must share one dtype")
     _check_f32(coords, "coords")
-    B, H1, W1 = int(levels[0].shape[0]), int(levels[0].shape[1]), int(levels[0].shape[2])
+    cap, H1, W1 = int(levels[0].shape[0]), int(levels[0].shape[1]), int(levels[0].shape[2])
     for l, p in enumerate(levels):
-        if tuple(p.shape) != (B, H1, W1, H1 >> l, W1 >> l):
-            raise RuntimeError(f"corr_pyramid_forward: pyramid[{l}] must be [{B},{H1},{W1},{H1 >> l},{W1 >> l}]")
+        if tuple(p.shape) != (cap, H1, W1, H1 >> l, W1 >> l):
+            raise RuntimeError(f"corr_pyramid_forward: pyramid[{l}] must be [{cap},{H1},{W1},{H1 >> l},{W1 >> l}]")
+    B = cap
+    if slots is not None:
+        _check_index(slots, "slots")
+        if slots.dim() != 1:
+            raise RuntimeError("corr_pyramid_forward: slots must be [B]")
+        B = int(slots.shape[0])
     if tuple(coords.shape) != (B, 2, H1, W1):
         raise RuntimeError("corr_pyramid_forward: coords must be [B,2,H1,W1]")
     r = int(radius)
     rd2 = (2 * r + 1) ** 2
     corr = torch.empty((B, len(levels) * rd2, H1, W1), dtype=levels[0].dtype, device=levels[0].device)
     ptrs = (ctypes.c_void_p * len(levels))(*[p.data_ptr() for p in levels])
-    _lib.check(lib.droid_corr_pyramid_forward(ptrs, coords.data_ptr(), corr.data_ptr(), B, H1, W1, r, len(levels),
-                                              _corr_dtype(levels[0], "pyramid"), _stream()), "corr_pyramid_forward")
+    if slots is None:
+        _lib.check(lib.droid_corr_pyramid_forward(ptrs, coords.data_ptr(), corr.data_ptr(), B, H1, W1, r, len(levels),
+                                                  _corr_dtype(levels[0], "pyramid"), _stream()), "corr_pyramid_forward")
+    else:
+        _lib.check(lib.droid_corr_pyramid_forward_slots(ptrs, slots.data_ptr(), coords.data_ptr(), corr.data_ptr(), B, cap,
+                                                        H1, W1, r, len(levels), _corr_dtype(levels[0], "pyramid"),
+                                                        _stream()), "corr_pyramid_forward")
     return [corr]
 
 
-def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0):
+def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0, slots=None):
     """CorrBlock.__init__ (droid_slam/modules/corr.py:24-38, 63-71) for the edges ii -> jj in one launch, from the
     feature buffer as DepthVideo holds it: fmaps [nbuf, ncam, C, h, w] (or [nbuf, C, h, w]) float16 / float32, channels
     first; ii, jj [E] int64.  Edge e correlates fmaps[ii[e], 0] / 4 with fmaps[jj[e], c] / 4, c = 1 for a stereo edge
@@ -446,6 +461,8 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0):
     With `out` (a list of capacity tensors [cap, h, w, h>>l, w>>l]) the edges are written to slots
     [offset, offset + E) -- every other slot is left as it is -- and views of those slots are returned: allocate the
     pyramid once and build new edges at offset = number of edges held, instead of CorrBlock.cat.
+    With `out` and `slots` ([E] int64 on the device, pairwise distinct) edge e is written to slot slots[e] instead, an
+    edge whose slot is outside [0, cap) is skipped, and `out` itself is returned (droid_corr_volume_pyramid_slots).
     The contract is in include/droid_backends_hip.h (droid_corr_volume_pyramid).  An addition."""
     lib = _lib.load()
     _check_input(fmaps, "fmaps")
@@ -463,6 +480,7 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0):
         raise RuntimeError("corr_volume_pyramid: ii and jj must be [E]")
     E = int(ii.shape[0])
     shapes = [(h, w, h >> l, w >> l) for l in range(levels)]
+    given_out = out is not None
     if out is None:
         if offset != 0:
             raise RuntimeError("corr_volume_pyramid: offset needs out")
@@ -476,6 +494,19 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0):
             if o.dtype != fmaps.dtype or o.dim() != 5 or tuple(o.shape[1:]) != shapes[l] or o.shape[0] != out[0].shape[0]:
                 raise RuntimeError(f"corr_volume_pyramid: out[{l}] must be [cap,{h},{w},{h >> l},{w >> l}] of {fmaps.dtype}")
     cap = int(out[0].shape[0]) if levels > 0 else 0
+    if slots is not None:
+        if not given_out:
+            raise RuntimeError("corr_volume_pyramid: slots needs out")
+        if offset != 0:
+            raise RuntimeError("corr_volume_pyramid: slots and offset exclude each other")
+        _check_index(slots, "slots")
+        if tuple(slots.shape) != (E,):
+            raise RuntimeError("corr_volume_pyramid: slots must be [E]")
+        ptrs = (ctypes.c_void_p * max(levels, 1))(*[o.data_ptr() for o in out])
+        _lib.check(lib.droid_corr_volume_pyramid_slots(fmaps.data_ptr(), ii.data_ptr(), jj.data_ptr(), ptrs,
+                                                       slots.data_ptr(), E, nbuf, ncam, C, h, w, levels, cap,
+                                                       _DT[fmaps.dtype], _stream()), "corr_volume_pyramid")
+        return out
     if offset < 0 or offset + E > cap:
         raise RuntimeError(f"corr_volume_pyramid: slots [{offset}, {offset + E}) do not fit the capacity {cap}")
     ptrs = (ctypes.c_void_p * max(levels, 1))(*[o.data_ptr() for o in out])

@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("DROID_HIP_LIB") or os.path.join(_HERE, "libdroid_back
 SYMBOLS = [
     "droid_abi_version", "droid_last_error",
     "droid_corr_index_forward", "droid_corr_index_backward", "droid_corr_pyramid_forward",
-    "droid_corr_volume_pyramid",
+    "droid_corr_volume_pyramid", "droid_corr_pyramid_forward_slots", "droid_corr_volume_pyramid_slots",
     "droid_altcorr_forward", "droid_altcorr_backward", "droid_altcorr_pyramid_forward",
     "droid_altcorr_pyramid_forward_f16",
     "droid_ba_workspace_bytes", "droid_ba", "droid_ba_prepare", "droid_ba_build", "droid_ba_build_packed",
@@ -59,6 +59,10 @@ def load() -> ctypes.CDLL:
     lib.droid_corr_pyramid_forward.argtypes = [ctypes.POINTER(vp), vp, vp] + [c_int] * 6 + [vp]
     lib.droid_corr_volume_pyramid.argtypes = ([vp, vp, vp, ctypes.POINTER(vp)] + [c_int] * 7
                                               + [ctypes.c_int64, ctypes.c_int64, c_int, vp])
+    lib.droid_corr_pyramid_forward_slots.argtypes = ([ctypes.POINTER(vp), vp, vp, vp, c_int, ctypes.c_int64]
+                                                     + [c_int] * 5 + [vp])
+    lib.droid_corr_volume_pyramid_slots.argtypes = ([vp, vp, vp, ctypes.POINTER(vp), vp] + [c_int] * 7
+                                                    + [ctypes.c_int64, c_int, vp])
     lib.droid_altcorr_forward.argtypes = [vp, vp, vp, vp] + [c_int] * 9 + [vp]
     lib.droid_altcorr_backward.argtypes = [vp] * 6 + [c_int] * 8 + [vp]
     lib.droid_altcorr_pyramid_forward.argtypes = [ctypes.POINTER(vp), vp, vp, vp, vp] + [c_int] * 7 + [vp]

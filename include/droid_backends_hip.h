@@ -77,6 +77,31 @@ int droid_corr_volume_pyramid(const void *fmaps, const int64_t *ii, const int64_
                               int E, int nbuf, int ncam, int C, int H, int W, int levels, int64_t slot0,
                               int64_t cap, int dtype, void *stream);
 
+/* The two operators above on capacity buffers whose slots are handed out in any order, so that dropping edges
+ * (FactorGraph.rm_factors, `self.corr = self.corr[~mask]`) edits a list of integers and moves no pyramid bytes.
+ * volumes[l] / levels_out[l]: HOST arrays of device pointers, level l = [cap, H1, W1, H1>>l, W1>>l] of dtype.
+ * slots: DEVICE array, [B] / [E] int64; the host never reads it, so its values are checked on the device.
+ *
+ * droid_corr_pyramid_forward_slots: batch entry b looks up the planes of slot slots[b]; coords [B,2,H1,W1] and
+ * corr [B, levels (2r+1)^2, H1, W1] stay indexed by b.  Bit-identical to droid_corr_pyramid_forward on the gathered
+ * copy volumes[l][slots]; two entries may name one slot.  A slot outside [0, cap) gives zeros for the whole output of
+ * that entry (the convention of an edge index outside [0, nbuf) below and in droid_altcorr_pyramid_forward) and reads
+ * nothing outside the buffers.  f16 / f32 / f64, radius 3 or 4, levels 1..8, B <= 65535.
+ *
+ * droid_corr_volume_pyramid_slots: edge e is written to slot slots[e], completely, with the bits
+ * droid_corr_volume_pyramid gives it; no other slot is touched.  An edge whose slot is outside [0, cap) is skipped:
+ * nothing is written for it.  Two edges of one call with the same slot violate the contract: which edge's bits end up
+ * there is unspecified (nothing outside that slot is written).  f16 / f32; shape limits as above.
+ *
+ * Both: cap < 1, a null slots with B (E) > 0, and every limit of the function above return DROID_E_ARG with a message.
+ * All argument checks are host-side and precede any HIP call; B == 0 / E == 0 launches nothing. */
+int droid_corr_pyramid_forward_slots(const void *const *volumes, const int64_t *slots, const float *coords,
+                                     void *corr, int B, int64_t cap, int H1, int W1, int radius, int levels,
+                                     int dtype, void *stream);
+int droid_corr_volume_pyramid_slots(const void *fmaps, const int64_t *ii, const int64_t *jj,
+                                    void *const *levels_out, const int64_t *slots, int E, int nbuf, int ncam,
+                                    int C, int H, int W, int levels, int64_t cap, int dtype, void *stream);
+
 /* corr_index_backward (droid.cpp:180-191 -> correlation_kernels.cu:157-185).
  * corr_grad [B,2r+1,2r+1,H1,W1] dtype ; volume_grad [B,H1,W1,H2,W2] dtype (written completely). */
 int droid_corr_index_backward(const float *coords, const void *corr_grad, void *volume_grad, int B,
