@@ -271,9 +271,10 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(
   const int k = blockIdx.x * 256 + threadIdx.x;
   const int HW = H * W;
   if (k >= HW) return;
-  const int ix = (int)inds[b];
+  const int64_t i64 = inds[b];  // checked before it is narrowed: 2^32 + 3 is not frame 3
   float cnt = 0.f;
-  if (ix >= 0 && ix < nbuf) {
+  if (i64 >= 0 && i64 < nbuf) {
+    const int ix = (int)i64;
     const Intr K = {intrinsics[0], intrinsics[1], intrinsics[2], intrinsics[3]};
     const float t = thresh[b];
     const float ui = (float)(k % W), vi = (float)(k / W);
@@ -316,31 +317,44 @@ void launch_frame_distance_matrix(const float* poses, const float* disps, const 
                      intr, dist, n, H, W, beta);
 }
 
+// projmap, reproject_motion, iproj and depth_filter put the edge (frame, selection) index on gridDim.y, which ends at
+// 65535: larger counts are launched in slabs of that many, each on the tail of its arrays.
+constexpr int GRID_Y_MAX = 65535;
+
 void launch_projmap(const float* poses, const float* disps, const float* intr, const int64_t* ii,
                     const int64_t* jj, int E, int nbuf, int H, int W, float* coords, float* valid,
                     hipStream_t s) {
-  hipLaunchKernelGGL(projmap_kernel, dim3((H * W + 255) / 256, E), dim3(256), 0, s, poses, disps,
-                     intr, ii, jj, coords, valid, nbuf, H, W);
+  const size_t HW = (size_t)H * W;
+  for (int e0 = 0; e0 < E; e0 += GRID_Y_MAX)
+    hipLaunchKernelGGL(projmap_kernel, dim3((H * W + 255) / 256, min(E - e0, GRID_Y_MAX)), dim3(256), 0, s, poses, disps,
+                       intr, ii + e0, jj + e0, coords + e0 * HW * 3, valid + e0 * HW, nbuf, H, W);
 }
 
 void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
                              const int64_t* ii, const int64_t* jj, const float* target, int E, int nbuf, int H,
                              int W, float* coords, float* valid, float* motn, hipStream_t s) {
-  hipLaunchKernelGGL(reproject_motion_kernel, dim3((H * W + 255) / 256, E), dim3(256), 0, s, poses, disps, intr,
-                     intr_stride, ii, jj, target, coords, valid, motn, nbuf, H, W);
+  const size_t HW = (size_t)H * W;
+  for (int e0 = 0; e0 < E; e0 += GRID_Y_MAX)
+    hipLaunchKernelGGL(reproject_motion_kernel, dim3((H * W + 255) / 256, min(E - e0, GRID_Y_MAX)), dim3(256), 0, s,
+                       poses, disps, intr, intr_stride, ii + e0, jj + e0, target ? target + e0 * HW * 2 : nullptr,
+                       coords + e0 * HW * 2, valid + e0 * HW, motn ? motn + e0 * HW * 4 : nullptr, nbuf, H, W);
 }
 
 void launch_iproj(const float* poses, const float* disps, const float* intr, int nm, int H, int W,
                   float* points, hipStream_t s) {
-  hipLaunchKernelGGL(iproj_kernel, dim3((H * W + 255) / 256, nm), dim3(256), 0, s, poses, disps,
-                     intr, points, H, W);
+  const size_t HW = (size_t)H * W;
+  for (int f0 = 0; f0 < nm; f0 += GRID_Y_MAX)
+    hipLaunchKernelGGL(iproj_kernel, dim3((H * W + 255) / 256, min(nm - f0, GRID_Y_MAX)), dim3(256), 0, s,
+                       poses + 7 * (size_t)f0, disps + f0 * HW, intr, points + f0 * HW * 3, H, W);
 }
 
 void launch_depth_filter(const float* poses, const float* disps, const float* intr,
                          const int64_t* ix, const float* thresh, int num, int nbuf, int H, int W,
                          float* counter, hipStream_t s) {
-  hipLaunchKernelGGL(depth_filter_kernel, dim3((H * W + 255) / 256, num), dim3(256), 0, s, poses,
-                     disps, intr, ix, thresh, counter, nbuf, H, W);
+  const size_t HW = (size_t)H * W;
+  for (int b0 = 0; b0 < num; b0 += GRID_Y_MAX)
+    hipLaunchKernelGGL(depth_filter_kernel, dim3((H * W + 255) / 256, min(num - b0, GRID_Y_MAX)), dim3(256), 0, s, poses,
+                       disps, intr, ix + b0, thresh + b0, counter + b0 * HW, nbuf, H, W);
 }
 
 }  // namespace droid

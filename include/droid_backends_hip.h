@@ -302,7 +302,7 @@ int droid_frame_distance_matrix(const float *poses, const float *disps, const fl
                                 int nbuf, int H, int W, float beta, float *dist, void *stream);
 
 /* projmap (droid.cpp:139-154 -> droid_kernels.cu:427-516, :1463-1488):
- * coords [E,H,W,3] f32 (channel 2 zero), valid [E,H,W,1] f32 */
+ * coords [E,H,W,3] f32 (channel 2 zero), valid [E,H,W,1] f32.  Any E an int holds (launched in slabs of 65535). */
 int droid_projmap(const float *poses, const float *disps, const float *intrinsics,
                   const int64_t *ii, const int64_t *jj, int E, int nbuf, int H, int W,
                   float *coords, float *valid, void *stream);
@@ -315,17 +315,20 @@ int droid_projmap(const float *poses, const float *disps, const float *intrinsic
  *   (`motn = cat(coords1 - coords0, target - coords1).permute(0,1,4,2,3).clamp(-64, 64)`).
  * intrinsics: [nbuf,4] with intr_stride = 4, or one [4] for all frames with intr_stride = 0.
  * target [E,H,W,2] f32 and motn [E,4,H,W] f32 may both be null (plain reproject).
- * coords [E,H,W,2] f32, valid [E,H,W,1] f32.  Edges with an index outside [0,nbuf) produce zeros. */
+ * coords [E,H,W,2] f32, valid [E,H,W,1] f32.  Edges with an index outside [0,nbuf) produce zeros.
+ * Any E an int holds (launched in slabs of 65535). */
 int droid_reproject_motion(const float *poses, const float *disps, const float *intrinsics, int intr_stride,
                            const int64_t *ii, const int64_t *jj, const float *target, int E, int nbuf, int H,
                            int W, float *coords, float *valid, float *motn, void *stream);
 
-/* iproj (droid.cpp:157-166 -> droid_kernels.cu:779-850, :1518-1541): points [nm,H,W,3] f32 */
+/* iproj (droid.cpp:157-166 -> droid_kernels.cu:779-850, :1518-1541): points [nm,H,W,3] f32.
+ * Any nm an int holds (launched in slabs of 65535). */
 int droid_iproj(const float *poses, const float *disps, const float *intrinsics, int nm, int H,
                 int W, float *points, void *stream);
 
 /* depth_filter (droid.cpp:220-234 -> droid_kernels.cu:661-775, :1491-1515):
- * counter [num,H,W] f32 (written completely) */
+ * counter [num,H,W] f32 (written completely).  Any num an int holds (launched in slabs of 65535); an index outside
+ * [0,nbuf), compared as the int64 it is, gives a zero plane. */
 int droid_depth_filter(const float *poses, const float *disps, const float *intrinsics,
                        const int64_t *ix, const float *thresh, int num, int nbuf, int H, int W,
                        float *counter, void *stream);

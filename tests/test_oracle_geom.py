@@ -106,3 +106,82 @@ def test_geom_golden_vectors():
     assert np.abs(motn - g["motn"]).max() < 1e-9
     cnt = geom.depth_filter(g["df_poses"], g["disps"], g["df_intrinsics"], g["df_ix"], g["df_thresh"])
     assert np.array_equal(cnt, g["df_counter"])
+
+
+def _wild(rng, N=6, H=11, W=14):
+    poses, disps, K = _scene(rng, N, H, W)
+    q = rng.normal(size=(N, 4)); q /= np.linalg.norm(q, axis=1, keepdims=True)
+    poses[:, 3:] = q
+    poses[:, :3] = rng.normal(0, 0.4, (N, 3))
+    ii, jj = np.array([0, 1, 2, 3, 4, 5, 0]), np.array([1, 2, 0, 5, 3, 4, 4])
+    return poses, disps, K, ii, jj
+
+
+def test_projmap_frame_distance_iproj_agree_with_the_c_restatement(oracle):
+    """Two restatements written apart (numpy here, C in oracle/ba_oracle_impl.h) of the same three kernels."""
+    rng = np.random.default_rng(6)
+    poses, disps, K, ii, jj = _wild(rng)
+    c, v, m = geom.projmap(poses, disps, K, ii, jj, margins=True)
+    oc, ov = oracle.projmap(poses, disps, K, ii, jj)
+    assert np.array_equal(v, ov) and np.abs(c - oc).max() < 1e-9 * np.abs(oc).max()
+    assert (m["Z"] <= 0.01).any() and (m["Z"] > 0.25).any()
+    for beta in (0.0, 0.3, 1.0):
+        d, fm = geom.frame_distance(poses, disps, K, ii, jj, beta, margins=True)
+        od = oracle.frame_distance(poses, disps, K, ii, jj, beta)
+        assert np.array_equal(d == 1000.0, od == 1000.0) and np.abs(d - od).max() < 1e-9 * np.abs(od).max()
+        d2, share = geom.frame_distance_from_parts(fm, beta)
+        assert np.array_equal(d, d2) and np.array_equal(share, fm["share"])
+    assert np.abs(geom.iproj(poses, disps, K) - oracle.iproj(poses, disps, K)).max() < 1e-12
+
+
+def test_margins_are_the_quantities_the_decisions_are_taken_on():
+    """Pure z translation: Z = 1 + d tz in closed form, mag = |X0| + |X1| + 1 + |d| |tz|, the band 64 * 2^-24 * mag."""
+    rng = np.random.default_rng(7)
+    poses, disps, K = _scene(rng)
+    poses[1, 2] = -0.9
+    _, valid, m = geom.projmap(poses, disps, K, np.array([0]), np.array([1]), margins=True)
+    y, x = np.meshgrid(np.arange(12.0), np.arange(16.0), indexing="ij")
+    assert np.abs(m["Z"][0] - (1 - 0.9 * disps[0])).max() < 1e-15
+    assert np.abs(m["mag"][0] - (np.abs((x - K[2]) / K[0]) + np.abs((y - K[3]) / K[1]) + 1 + 0.9 * disps[0])).max() < 1e-12
+    assert np.array_equal(valid[0, ..., 0] == 1.0, 1 - 0.9 * disps[0] > 0.25)
+    assert geom.z_band(2.0) == 64 * 2.0 ** -24 * 2.0
+    _, rvalid, r = geom.reproject(poses, disps, K, np.array([0]), np.array([1]), margins=True)
+    assert np.array_equal(r["Z"], m["Z"]) and np.array_equal(rvalid[0, ..., 0] == 1.0, r["Z"][0] > 0.2)
+    assert np.array_equal(r["Zc"] == 1.0, r["Z"] < 0.1)
+    d, fm = geom.frame_distance(poses, disps, K, np.array([0]), np.array([1]), 0.3, margins=True)
+    assert np.array_equal(fm["Z"], fm["Zt"]) and fm["share"][0] == (m["Z"] > 0.25).sum() / (192 + 1e-8)
+    # the coordinate scale bounds the change of the coordinate under a change of X and Z by z_band
+    s = geom.coord_scale(K[0], K[2], m["X"][..., 0], m["Z"], m["mag"])
+    db = geom.z_band(m["mag"], 1.0)
+    u = lambda X, Z: K[0] * X / Z + K[2]
+    far = np.abs(m["Z"]) > 0.005
+    assert (np.abs(u(m["X"][..., 0] + db, m["Z"] - np.sign(m["Z"]) * db) - u(m["X"][..., 0], m["Z"]))[far] <= 1.01 * geom.EPS32 * s[far]).all()
+
+
+def test_iproj_zero_disparity_and_stored_pose():
+    poses = np.zeros((1, 7)); poses[0, 6] = 1.0; poses[0, :3] = [1.0, 2.0, 3.0]
+    disps = np.full((1, 2, 2), 0.5); disps[0, 0, 0] = 0.0
+    K = np.array([2.0, 2.0, 0.5, 0.5])
+    with np.errstate(all="ignore"):
+        pts = geom.iproj(poses, disps, K)
+    assert np.allclose(pts[0, 1, 1], np.array([0.25, 0.25, 1.0]) / 0.5 + [1, 2, 3])    # X0 / d + t
+    assert np.isinf(pts[0, 0, 0]).all() and np.array_equal(np.sign(pts[0, 0, 0]), [-1.0, -1.0, 1.0])
+
+
+def test_depth_filter_band_names_threshold_and_corner_decisions():
+    """Static scene: every decision is far from the threshold -> empty band.  A neighbour whose inverse disparity
+    sits a float32 rounding from the threshold, or a projection a rounding from an integer next to a corner that
+    decides differently, is in the band, and only those."""
+    poses = np.zeros((9, 7)); poses[:, 6] = 1.0
+    disps = np.full((9, 10, 12), 0.7)
+    K = np.array([20.0, 20.0, 5.5, 4.5])
+    cnt, band = geom.depth_filter(poses, disps, K, np.array([4]), np.array([0.01]), margins=True)
+    assert np.all(cnt[0, :-1, :-1] == 5)
+    # integer projections (identity poses) sit ON the grid: the corner one step back decides alike except at the
+    # border, where it leaves the image -- those pixels are the band
+    b = band()
+    assert not b[0, :, 1:-1, 1:-1].any() and b[0, :5, 0, :].all() and not b[0, 5].any()
+    disps[3] = 1.0 / (1.0 / 0.7 + 0.01 * (1 + 1e-7))          # neighbour ix-1: |diff| = thresh (1 + 1e-7)
+    cnt2, band2 = geom.depth_filter(poses, disps, K, np.array([4]), np.array([0.01]), margins=True)
+    assert np.all(cnt2[0, :-1, :-1] == 4) and band2()[0, 0, :-1, :-1].all() and not band2()[0, 1, 1:-1, 1:-1].any()
+    assert not band2(0.0)[0, 1, 1:-1, 1:-1].any()
