@@ -47,6 +47,19 @@ def test_host_side_argument_checks_need_no_gpu(backends):
     assert lib.droid_chol_scratch_doubles(n) >= (n + 1) * 1536 + (2 * 24 + 300) * 4096
 
 
+def test_chol_scratch_grows_with_n(backends):
+    """Over the sizes of the accuracy table (tests/chol_cases.py): strictly monotone, and never below the augmented
+    system with 128-byte rows that opens the buffer.  The header's 128-byte claim is about the buffer's ADDRESS (the
+    caller aligns it) and about the row pitch; the total is a count of doubles and need not be a multiple of 16."""
+    import chol_cases
+    lib = backends._lib.load()
+    sizes = sorted({c.n for c in chol_cases.CASES})
+    need = [lib.droid_chol_scratch_doubles(n) for n in sizes]
+    assert all(a < b for a, b in zip(need, need[1:])), list(zip(sizes, need))
+    for n, d in zip(sizes, need):
+        assert d >= (n + 1) * ((n + 1 + 15) // 16 * 16), (n, d)
+
+
 def test_python_mirror_has_the_reference_operators(backends):
     for name in ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
                  "altcorr_backward", "corr_index_forward", "corr_index_backward"]:
