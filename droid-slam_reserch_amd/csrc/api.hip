@@ -2,10 +2,9 @@
 // checks, workspace carving, kernel launches on the caller's stream.  No synchronisation except
 // in droid_ba_status.
 #include <hip/hip_runtime.h>
+#include <stdarg.h>
 #include <stdio.h>
-#include <string.h>
 
-#include <algorithm>
 #include <map>
 #include <mutex>
 
@@ -86,8 +85,11 @@ static int* mirror_of(const void* ws) {
   return it == g_mirror.end() ? nullptr : it->second;
 }
 
-static int fail(int code, const char* fmt, const char* what) {
-  snprintf(g_err, sizeof(g_err), fmt, what);
+static int fail(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
   return code;
 }
 
@@ -132,24 +134,34 @@ int droid_corr_pyramid_forward(const void* const* volumes, const float* coords, 
   return check_hip("corr_pyramid_forward");
 }
 
+// droid_corr_volume_pyramid (slots == nullptr: edge e goes to slot slot0 + e) and droid_corr_volume_pyramid_slots (by_slots)
+static int corr_volume_pyramid_any(const char* name, bool by_slots, const void* fmaps, const int64_t* ii, const int64_t* jj,
+                                   void* const* levels_out, const int64_t* slots, int E, int nbuf, int ncam, int C, int H, int W,
+                                   int levels, int64_t slot0, int64_t cap, int dtype, void* stream) {
+  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "%s: bad %s", name, "dtype (f16 or f32)");
+  if (E < 0 || nbuf <= 0 || ncam < 1 || ncam > 2) return fail(DROID_E_ARG, "%s: bad %s", name, "E / nbuf / ncam");
+  if (C <= 0 || C % 32 != 0 || C > 256) return fail(DROID_E_ARG, "%s: bad %s", name, "C (a multiple of 32, at most 256)");
+  if (H < 8 || W < 8 || W % 8 != 0 || ((long long)H * W) % 16 != 0 || (long long)H * W > (1 << 24))
+    return fail(DROID_E_ARG, "%s: bad %s", name, "map size (H, W >= 8, W % 8 == 0, H * W % 16 == 0)");
+  if (levels < 1 || levels > 4) return fail(DROID_E_ARG, "%s: bad %s", name, "levels (1 .. 4)");
+  if (by_slots && cap < 1) return fail(DROID_E_ARG, "%s: bad %s", name, "cap (at least 1)");
+  if (!by_slots && (slot0 < 0 || cap < 0 || slot0 + E > cap)) return fail(DROID_E_ARG, "%s: %s", name, "slot0 + E exceeds cap");
+  if (E == 0) return DROID_OK;
+  if (by_slots && !slots) return fail(DROID_E_ARG, "%s: null %s", name, "slots");
+  if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "%s: null %s", name, "pointer");
+  for (int l = 0; l < levels; l++)
+    if (!levels_out[l]) return fail(DROID_E_ARG, "%s: null %s", name, "pyramid level");
+  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, slots,
+                                      (long long)cap, dtype, (hipStream_t)stream);
+  if (rc) return fail(rc, "%s: %s", name, "unsupported configuration");
+  return check_hip(name);
+}
+
 int droid_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
                               int nbuf, int ncam, int C, int H, int W, int levels, int64_t slot0, int64_t cap, int dtype,
                               void* stream) {
-  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "dtype (f16 or f32)");
-  if (E < 0 || nbuf <= 0 || ncam < 1 || ncam > 2) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "E / nbuf / ncam");
-  if (C <= 0 || C % 32 != 0 || C > 256) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "C (a multiple of 32, at most 256)");
-  if (H < 8 || W < 8 || W % 8 != 0 || ((long long)H * W) % 16 != 0 || (long long)H * W > (1 << 24))
-    return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "map size (H, W >= 8, W % 8 == 0, H * W % 16 == 0)");
-  if (levels < 1 || levels > 4) return fail(DROID_E_ARG, "corr_volume_pyramid: bad %s", "levels (1 .. 4)");
-  if (slot0 < 0 || cap < 0 || slot0 + E > cap) return fail(DROID_E_ARG, "corr_volume_pyramid: %s", "slot0 + E exceeds cap");
-  if (E == 0) return DROID_OK;
-  if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!levels_out[l]) return fail(DROID_E_ARG, "corr_volume_pyramid: null %s", "pyramid level");
-  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, nullptr,
-                                      (long long)cap, dtype, (hipStream_t)stream);
-  if (rc) return fail(rc, "corr_volume_pyramid: %s", "unsupported configuration");
-  return check_hip("corr_volume_pyramid");
+  return corr_volume_pyramid_any("corr_volume_pyramid", false, fmaps, ii, jj, levels_out, nullptr, E, nbuf, ncam, C, H, W,
+                                 levels, slot0, cap, dtype, stream);
 }
 
 int droid_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, const float* coords, void* corr,
@@ -174,23 +186,8 @@ int droid_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* 
 int droid_corr_volume_pyramid_slots(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out,
                                     const int64_t* slots, int E, int nbuf, int ncam, int C, int H, int W, int levels,
                                     int64_t cap, int dtype, void* stream) {
-  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "dtype (f16 or f32)");
-  if (E < 0 || nbuf <= 0 || ncam < 1 || ncam > 2) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "E / nbuf / ncam");
-  if (C <= 0 || C % 32 != 0 || C > 256)
-    return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "C (a multiple of 32, at most 256)");
-  if (H < 8 || W < 8 || W % 8 != 0 || ((long long)H * W) % 16 != 0 || (long long)H * W > (1 << 24))
-    return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "map size (H, W >= 8, W % 8 == 0, H * W % 16 == 0)");
-  if (levels < 1 || levels > 4) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "levels (1 .. 4)");
-  if (cap < 1) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: bad %s", "cap (at least 1)");
-  if (E == 0) return DROID_OK;
-  if (!slots) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "slots");
-  if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!levels_out[l]) return fail(DROID_E_ARG, "corr_volume_pyramid_slots: null %s", "pyramid level");
-  int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, 0, slots, (long long)cap,
-                                      dtype, (hipStream_t)stream);
-  if (rc) return fail(rc, "corr_volume_pyramid_slots: %s", "unsupported configuration");
-  return check_hip("corr_volume_pyramid_slots");
+  return corr_volume_pyramid_any("corr_volume_pyramid_slots", true, fmaps, ii, jj, levels_out, slots, E, nbuf, ncam, C, H, W,
+                                 levels, 0, cap, dtype, stream);
 }
 
 int droid_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
@@ -263,13 +260,8 @@ int droid_altcorr_backward(const float* fmap1, const float* fmap2, const float* 
 }
 
 // ---------------------------------------------------------------------------- bundle adjustment
-static int ba_check(int E, int nbuf, int H, int W, int t0, int t1, int M, int motion_only) {
-  if (E < 0 || nbuf <= 0 || H <= 0 || W <= 0) return fail(DROID_E_ARG, "ba: bad %s", "sizes");
-  if (t0 < 0 || t1 <= t0 || t1 > nbuf) return fail(DROID_E_ARG, "ba: bad %s", "window [t0,t1)");
-  if (M < 0 || M > nbuf) return fail(DROID_E_ARG, "ba: bad %s", "depth-slot count (eta rows)");
-  if (!motion_only && M == 0) return fail(DROID_E_ARG, "ba: %s", "eta has no rows");
-  return DROID_OK;
-}
+// The dimensions every BA entry point receives, filled once per entry point
+struct BaDims { int E, nbuf, H, W, M, t0, t1, motion_only; };
 
 size_t droid_ba_workspace_bytes(int E, int nbuf, int H, int W, int t0, int t1, int M) {
   BaView v;
@@ -277,12 +269,13 @@ size_t droid_ba_workspace_bytes(int E, int nbuf, int H, int W, int t0, int t1, i
   return ba_carve(v, nullptr, E, nbuf, H, W, t0, t1, M);
 }
 
-static int ba_view(BaView& v, void* ws, size_t ws_bytes, int E, int nbuf, int H, int W, int t0,
-                   int t1, int M, int motion_only) {
-  int rc = ba_check(E, nbuf, H, W, t0, t1, M, motion_only);
-  if (rc) return rc;
+static int ba_view(BaView& v, void* ws, size_t ws_bytes, const BaDims& d) {
+  if (d.E < 0 || d.nbuf <= 0 || d.H <= 0 || d.W <= 0) return fail(DROID_E_ARG, "ba: bad %s", "sizes");
+  if (d.t0 < 0 || d.t1 <= d.t0 || d.t1 > d.nbuf) return fail(DROID_E_ARG, "ba: bad %s", "window [t0,t1)");
+  if (d.M < 0 || d.M > d.nbuf) return fail(DROID_E_ARG, "ba: bad %s", "depth-slot count (eta rows)");
+  if (!d.motion_only && d.M == 0) return fail(DROID_E_ARG, "ba: %s", "eta has no rows");
   if (!ws) return fail(DROID_E_ARG, "ba: null %s", "workspace");
-  const size_t need = ba_carve(v, ws, E, nbuf, H, W, t0, t1, motion_only ? 0 : M);
+  const size_t need = ba_carve(v, ws, d.E, d.nbuf, d.H, d.W, d.t0, d.t1, d.motion_only ? 0 : d.M);
   if (ws_bytes < need) return fail(DROID_E_WORKSPACE, "ba: %s", "workspace too small");
   return DROID_OK;
 }
@@ -291,7 +284,7 @@ int droid_ba_prepare(const int64_t* ii, const int64_t* jj, int E, int nbuf, int 
                      int t0, int t1, int own0, int own1, int motion_only, void* workspace,
                      size_t workspace_bytes, void* stream) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, motion_only});
   if (rc) return rc;
   if (E > 0 && (!ii || !jj)) return fail(DROID_E_ARG, "ba: null %s", "edge arrays");
   v.own0 = own0 < 0 ? 0 : own0;
@@ -304,22 +297,48 @@ int droid_ba_prepare(const int64_t* ii, const int64_t* jj, int E, int nbuf, int 
   return check_hip("ba_prepare");
 }
 
-} // extern "C"
+}  // extern "C"
+// One Gauss-Newton iteration is these two sequences of launches; the product (droid_ba_build*, droid_ba_solve_update, and
+// through them droid_ba) and droid_ba_profile_iteration both enqueue it here.  between() is called after every group of
+// launches: the three build stages, the factorisation, the back-substitution, the update.
+template <class Between>
+static void enqueue_build(const BaView& v, const float* poses, const float* disps, const float* intrinsics,
+                          const float* disps_sens, const float* targets, const float* weights, const float* eta,
+                          const int64_t* ii, const int64_t* jj, bool motion_only, hipStream_t s, Between between) {
+  const BaLaunchPlan plan = ba_launch_plan(v);
+  for (int stage = 0; stage < 3; stage++) {
+    launch_build_stage(v, plan, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only, stage, s);
+    between();
+  }
+}
+template <class Between>
+static void enqueue_solve_update(const BaView& v, float* poses, float* disps, const float* intrinsics, const float* weights,
+                                 const int64_t* ii, const int64_t* jj, float lm, float ep, bool motion_only, float* dx_out,
+                                 float* dz_out, int* status_mirror, hipStream_t s, Between between) {
+  const CholSystem c(v);   // launch_chol_solve (chol.hip), spelled out so that between() fits in
+  if (v.E <= 0) launch_chol_preset(c, s);   // with edges, the build's assemble units have preset the solver scratch
+  const bool single = launch_chol_factor(c, (double)lm, (double)ep, s);
+  between();
+  launch_chol_backsolve(c, single, s);
+  between();
+  launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, dx_out, dz_out, motion_only, s, status_mirror);
+  between();
+}
+
 static int ba_build_impl(const float* poses, const float* disps, const float* intrinsics,
                          const float* disps_sens, const float* targets, const float* weights,
-                         const float* eta, const int64_t* ii, const int64_t* jj, int E, int nbuf, int H,
-                         int W, int M, int t0, int t1, int motion_only, void* workspace,
+                         const float* eta, const int64_t* ii, const int64_t* jj, const BaDims& d, void* workspace,
                          size_t workspace_bytes, void* stream, int packed) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, d);
   if (rc) return rc;
   v.packed = packed;
   hints_of(v, workspace, false);
   if (!poses || !disps || !intrinsics) return fail(DROID_E_ARG, "ba: null %s", "state pointer");
-  if (E > 0 && (!targets || !weights || !ii || !jj)) return fail(DROID_E_ARG, "ba: null %s", "edge data");
-  if (!motion_only && (!eta || !disps_sens)) return fail(DROID_E_ARG, "ba: null %s", "eta/disps_sens");
-  launch_build(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj,
-               motion_only != 0, (hipStream_t)stream);
+  if (d.E > 0 && (!targets || !weights || !ii || !jj)) return fail(DROID_E_ARG, "ba: null %s", "edge data");
+  if (!d.motion_only && (!eta || !disps_sens)) return fail(DROID_E_ARG, "ba: null %s", "eta/disps_sens");
+  enqueue_build(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, d.motion_only != 0,
+                (hipStream_t)stream, [] {});
   return check_hip("ba_build");
 }
 extern "C" {
@@ -329,8 +348,8 @@ int droid_ba_build(const float* poses, const float* disps, const float* intrinsi
                    const float* eta, const int64_t* ii, const int64_t* jj, int E, int nbuf, int H,
                    int W, int M, int t0, int t1, int motion_only, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  return ba_build_impl(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, E, nbuf, H, W, M, t0, t1,
-                       motion_only, workspace, workspace_bytes, stream, 0);
+  return ba_build_impl(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj,
+                       BaDims{E, nbuf, H, W, M, t0, t1, motion_only}, workspace, workspace_bytes, stream, 0);
 }
 
 int droid_ba_build_packed(const float* poses, const float* disps, const float* intrinsics,
@@ -338,8 +357,8 @@ int droid_ba_build_packed(const float* poses, const float* disps, const float* i
                           const float* eta, const int64_t* ii, const int64_t* jj, int E, int nbuf, int H,
                           int W, int M, int t0, int t1, int motion_only, void* workspace,
                           size_t workspace_bytes, void* stream) {
-  return ba_build_impl(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, E, nbuf, H, W, M, t0, t1,
-                       motion_only, workspace, workspace_bytes, stream, 1);
+  return ba_build_impl(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj,
+                       BaDims{E, nbuf, H, W, M, t0, t1, motion_only}, workspace, workspace_bytes, stream, 1);
 }
 
 double* droid_ba_packed_system(void* workspace, int E, int nbuf, int H, int W, int t0, int t1, int M,
@@ -354,7 +373,7 @@ double* droid_ba_packed_system(void* workspace, int E, int nbuf, int H, int W, i
 int droid_ba_unpack_system(int E, int nbuf, int H, int W, int M, int t0, int t1, int motion_only, void* workspace,
                            size_t workspace_bytes, void* stream) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, motion_only});
   if (rc) return rc;
   launch_unpack_system(v, (hipStream_t)stream);
   return check_hip("ba_unpack_system");
@@ -391,7 +410,7 @@ int droid_ba_overlap_plan(int t0, int t1, int max_chunks, int* nchunks_out, size
 int droid_ba_unpack_chunk(int E, int nbuf, int H, int W, int M, int t0, int t1, int chunk, int max_chunks, float lm,
                           float ep, int epoch, void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, 0);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, 0});
   if (rc) return rc;
   int brow[33];
   if (max_chunks < 1 || max_chunks > 32) return fail(DROID_E_ARG, "ba_unpack_chunk: bad %s", "max_chunks");
@@ -415,7 +434,7 @@ int droid_ba_solve_update_overlap(float* poses, float* disps, const float* intri
                                   int t0, int t1, int epoch, int motion_only, float* dx_out, float* dz_out,
                                   void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, motion_only});
   if (!rc) rc = solve_update_check(poses, disps, intrinsics, weights, ii, jj, E, motion_only);
   if (rc) return rc;
   if (E <= 0 || epoch <= 0) return fail(DROID_E_ARG, "ba_solve_update_overlap: needs %s", "edges (the build presets the solver scratch) and epoch > 0");
@@ -434,14 +453,11 @@ int droid_ba_solve_update(float* poses, float* disps, const float* intrinsics, c
                           int t0, int t1, float lm, float ep, int motion_only, float* dx_out,
                           float* dz_out, void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, motion_only});
   if (!rc) rc = solve_update_check(poses, disps, intrinsics, weights, ii, jj, E, motion_only);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // with edges, droid_ba_build's assemble kernel has preset the solver scratch
-  launch_chol_solve(CholSystem(v), (double)lm, (double)ep, s, E > 0);
-  launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, dx_out, dz_out, motion_only != 0, s,
-                mirror_of(workspace));
+  enqueue_solve_update(v, poses, disps, intrinsics, weights, ii, jj, lm, ep, motion_only != 0, dx_out, dz_out,
+                       mirror_of(workspace), (hipStream_t)stream, [] {});
   return check_hip("ba_solve_update");
 }
 
@@ -474,26 +490,20 @@ int droid_ba_profile_iteration(float* poses, float* disps, const float* intrinsi
                                int motion_only, void* workspace, size_t workspace_bytes,
                                void* stream, float* stage_ms) {
   BaView v;
-  int rc = ba_view(v, workspace, workspace_bytes, E, nbuf, H, W, t0, t1, M, motion_only);
+  int rc = ba_view(v, workspace, workspace_bytes, BaDims{E, nbuf, H, W, M, t0, t1, motion_only});
   if (rc) return rc;
   hints_of(v, workspace, false);
   if (!stage_ms) return fail(DROID_E_ARG, "ba_profile: null %s", "stage_ms");
   hipStream_t s = (hipStream_t)stream;
   hipEvent_t ev[7];
   for (auto& e : ev) (void)hipEventCreate(&e);
-  (void)hipEventRecord(ev[0], s);
-  for (int stage = 0; stage < 3; stage++) {   // launch_build, stage by stage
-    launch_build_stage(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, stage, s);
-    (void)hipEventRecord(ev[stage + 1], s);
-  }
-  const CholSystem c(v);   // launch_chol_solve as droid_ba_solve_update calls it, with an event between its halves
-  if (E <= 0) launch_chol_preset(c, s);
-  const bool single = launch_chol_factor(c, (double)lm, (double)ep, s);
-  (void)hipEventRecord(ev[4], s);
-  launch_chol_backsolve(c, single, s);
-  (void)hipEventRecord(ev[5], s);
-  launch_update(v, poses, disps, intrinsics, weights, ii, jj, v.xsol, nullptr, nullptr, motion_only != 0, s);
-  (void)hipEventRecord(ev[6], s);
+  int nev = 0;
+  auto record = [&] { (void)hipEventRecord(ev[nev++], s); };
+  record();
+  // the product's iteration, without outputs and without a status mirror
+  enqueue_build(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, s, record);
+  enqueue_solve_update(v, poses, disps, intrinsics, weights, ii, jj, lm, ep, motion_only != 0, nullptr, nullptr, nullptr, s,
+                       record);
   hipError_t e = hipEventSynchronize(ev[6]);
   stage_ms[3] = 0.0f;
   for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&stage_ms[k < 3 ? k : k + 1], ev[k], ev[k + 1]);

@@ -108,13 +108,22 @@ struct BaView {
   int* ov_ready;           // [block columns of the system] overlap mode: epoch of the last iteration whose reduced columns are in `sys`
 };
 
-struct BaSizes {
-  size_t total;
-};
-
-// Carves `ws` (may be null: size query only) into the view.  Host-only arithmetic.
+// Launch geometry of one iteration.  ba_carve sizes buffers with these numbers and ba_launch_plan (below) turns them into
+// grids: nothing else on the host decides a grid of the build phase.
 constexpr int SY_WGS = 1024;  // (slot, pixel range) workgroups of the class-1 SYRK launch: four per CU balance the uneven slots (A/B 512 / 768 / 1024 / 1536 / 2048: 270 / 265 / 253 / 262 / 270 us at 256 slots)
 constexpr int S2_WGS = 1536;  // (slot, pixel range) workgroups of the sparse Schur launch
+constexpr int SF_WGS = 1536;  // (slot, pixel range) workgroups of the block-pair Schur launch
+constexpr int LIN_WGS = 1536; // (slot, pixel chunk, edge range) workgroups of the linearisation launch
+constexpr int LIN_ZERO_WGS = 192;  // workgroups of the linearisation launch that clear the system instead
+constexpr int SF_TP = 64;     // pixels per LDS tile of the block-pair Schur kernel; 4 threads per pixel split the edges
+// Dense slots (more than 16 entries) are served by the SYRK-only kernels.
+constexpr int SW_MID = 256;   // rows (incl. the w row) served by the two-workgroups-per-CU variant (42 entries; two staging rounds of 128 rows)
+constexpr int SW_BIG = 512;   // rows served by the one-per-CU variant (85 entries)
+constexpr int tri_tiles16(int rows) { return (rows / 16) * (rows / 16 + 1) / 2; }
+constexpr int SY_T1 = tri_tiles16(SW_MID), SY_T2 = tri_tiles16(SW_BIG);  // 16x16 tiles (1 KB of fp32 each) of a class-1 / class-2 slot's lower triangle: 136 / 528
+constexpr int SY_FOLD_GROUPS = SY_T1 / 4;  // grid y of the SYRK fold: four waves per workgroup, one class-1 tile per wave
+
+// Carves `ws` (may be null: size query only) into the view.  Host-only arithmetic.
 inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t0, int t1, int M) {
   v.E = E; v.nbuf = nbuf; v.H = H; v.W = W; v.HW = H * W;
   v.t0 = t0; v.t1 = t1; v.P = t1 - t0; v.M = M;
@@ -155,7 +164,7 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
   if (v.wide) {
     // pixel splits of the SYRK launches: enough (slot, range) workgroups to fill 256 CUs four times over (class 1: one 12-wave workgroup per
     // CU; class 2: four shares per pair); a split costs a set of partial tiles, no atomics.  A launch has M * ns pairs at most:
-    // 136 (class 1: <= 256 rows) or 528 (class 2: <= 512 rows) tiles of 1 KB each
+    // SY_T1 (class 1: <= SW_MID rows) or SY_T2 (class 2: <= SW_BIG rows) tiles of 1 KB each
     const int stages = v.HW / 32;
     int nsw = (SY_WGS + M - 1) / M, nsb = (256 + 4 * M - 1) / (4 * M);
     nsw = nsw < 2 ? 2 : (nsw > stages ? stages : nsw);
@@ -163,14 +172,14 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
     if (nsw > 16) nsw = 16;  // SY_MAXSPLIT (ba_kernels.hip): the kernels never use more ranges per slot
     if (nsb > 16) nsb = 16;
     v.sy_ns[0] = nsw; v.sy_ns[1] = nsb;
-    v.sy_part[0] = static_cast<float*>(take(sizeof(float) * ((size_t)M * nsw * 136 * 256 + 64)));
-    v.sy_part[1] = static_cast<float*>(take(sizeof(float) * ((size_t)M * nsb * 528 * 256 + 64)));
+    v.sy_part[0] = static_cast<float*>(take(sizeof(float) * ((size_t)M * nsw * SY_T1 * 256 + 64)));
+    v.sy_part[1] = static_cast<float*>(take(sizeof(float) * ((size_t)M * nsb * SY_T2 * 256 + 64)));
   }
   // few depth slots (edge-sharded ranks, small windows): split every slot's edges over several
   // workgroups so that the linearisation still fills the chip
   v.zsplit = 1;
   if (M > 0) {
-    const int z = 1536 / (M * v.nch);
+    const int z = LIN_WGS / (M * v.nch);
     v.zsplit = z < 1 ? 1 : (z > 8 ? 8 : z);
   }
   v.zpart = nullptr;
@@ -208,6 +217,29 @@ __host__ __device__ inline int solver_preset_words(const BaView& v) {
 // 32 KB blocks of the panel-tile hand-over slots (ldiag + chol_lfin_offset), preset to 0xFF bytes the same way
 __host__ __device__ inline int solver_preset_tiles(const BaView& v) { return v.n > 0 ? (int)chol_tiles(v.n) : 0; }
 
+// Launch plan of one iteration's build phase: every grid size launch_build_stage uses that ba_carve has not already
+// put into the view (zsplit, s2_split, sy_ns).  Host-only arithmetic.
+struct BaLaunchPlan {
+  int zero_wgs;       // workgroups of the linearisation launch that clear the system
+  int asm_units;      // assemble units: one per edge + the presets of the solver scratch; 0 without edges
+  dim3 schur2;        // grid of the sparse Schur launch: (slots + spare columns that take the assemble units, pixel ranges)
+  int sf_split;       // pixel ranges per slot of the block-pair Schur launch
+  dim3 syrk[2], fold; // grids of the two SYRK launches and of their fold (dense graphs only)
+};
+inline BaLaunchPlan ba_launch_plan(const BaView& v) {
+  BaLaunchPlan p;
+  p.zero_wgs = LIN_ZERO_WGS;
+  p.asm_units = v.E > 0 ? v.E + (solver_preset_words(v) + 1023) / 1024 + solver_preset_tiles(v) : 0;
+  p.schur2 = dim3(v.M + (p.asm_units + 4 * v.s2_split - 1) / (4 * v.s2_split), v.s2_split);
+  // pixel split so that small graphs still fill the chip (atomics grow with the split)
+  const int tiles = (v.HW + SF_TP - 1) / SF_TP, ns = SF_WGS / (v.M > 0 ? v.M : 1);
+  p.sf_split = ns < 1 ? 1 : (ns > tiles ? tiles : ns);
+  p.syrk[0] = dim3(v.M, v.sy_ns[0], 1);
+  p.syrk[1] = dim3(v.M, v.sy_ns[1], 4);
+  p.fold = dim3(v.M, SY_FOLD_GROUPS, 2);
+  return p;
+}
+
 // What one Cholesky solve works on: the augmented system S ((n+1) x ld, row n = rhs, factored in place), the
 // solution x [n], the scratch of the single-launch kernels (flags [chol_flag_words(n)], ldiag [chol_ldiag_doubles(n)])
 // and the failure word (1: not positive definite, 2: stalled grid).  Every solve expects x, the flags and the
@@ -226,12 +258,9 @@ struct CholSystem {
 void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStream_t s);
 // multi-GPU: expand the (all-reduced) packed system into the pitched matrix the solver factors in place
 void launch_unpack_system(const BaView& v, hipStream_t s);
-void launch_build(const BaView& v, const float* poses, const float* disps, const float* intr,
-                  const float* sens, const float* targets, const float* weights, const float* eta,
-                  const int64_t* ii, const int64_t* jj, bool motion_only, hipStream_t s);
-// stage: 0 memset+linearise, 1 assemble, 2 schur (measurement support)
-void launch_build_stage(const BaView& v, const float* poses, const float* disps, const float* intr,
-                        const float* sens, const float* targets, const float* weights,
+// One stage of the build phase, launched as `plan` (ba_launch_plan of v) says: 0 memset+linearise, 1 assemble, 2 schur
+void launch_build_stage(const BaView& v, const BaLaunchPlan& plan, const float* poses, const float* disps,
+                        const float* intr, const float* sens, const float* targets, const float* weights,
                         const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only,
                         int stage, hipStream_t s);
 // status_mirror: optional device-visible host words {status, depth slots} written at the end of the iteration

@@ -138,11 +138,7 @@ struct SlotMetaT {
 };
 typedef SlotMetaT<float> SlotMeta;
 
-constexpr int SF_TP = 64;             // pixels per LDS tile; 4 threads per pixel split the edges
-constexpr int SF_RB = 96;             // rows per block (16 entries)
-// Dense slots (more than 16 entries) are served by the SYRK-only kernel further down.
-constexpr int SW_MID = 256;   // rows (incl. the w row) served by the two-workgroups-per-CU variant (42 entries; two staging rounds of 128 rows)
-constexpr int SW_BIG = 512;   // rows served by the one-per-CU variant (85 entries)
+constexpr int SF_RB = 96;             // rows per block (16 entries); SF_TP, SW_MID and SW_BIG are in ba_internal.hpp
 constexpr int SY_MAXSPLIT = 16;  // pixel ranges per slot of the SYRK kernels (each adds one fp64 atomic per output entry)
 
 // which kernel serves a slot: 0 = ba_schur2_kernel, 1/2 = SYRK-only kernel (E rows from v.Ebuf),
@@ -1475,7 +1471,6 @@ __device__ __forceinline__ void tri_coords(int ti, int& ta, int& tb) {
 // slots of BASELINE configs[3], of which the 12 M atomics were ~135 us: profiles/r03_dense_syrk_ab.txt).
 // ------------------------------------------------------------------------------------------
 constexpr int SY_TPX = 32;  // pixels per stage
-constexpr int SY_T1 = 16 * 17 / 2, SY_T2 = 32 * 33 / 2;  // 16x16 tiles of a class-1 / class-2 slot's lower triangle (ba_internal.hpp sizes v.sy_part with the same numbers)
 
 // ------------------------------------------------------------------------------------------
 // S = B~ B~^T on the bf16 matrix pipe at fp32 accuracy (round 3).  Every fp32 operand B~ = E sqrt(Q) is split into three
@@ -2059,53 +2054,40 @@ void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStrea
   }
 }
 
-void launch_build_stage(const BaView& v, const float* poses, const float* disps, const float* intr,
-                        const float* sens, const float* targets, const float* weights,
+void launch_build_stage(const BaView& v, const BaLaunchPlan& plan, const float* poses, const float* disps,
+                        const float* intr, const float* sens, const float* targets, const float* weights,
                         const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only,
                         int stage, hipStream_t s) {
   const bool depth = !motion_only && v.M > 0;
   switch (stage) {
-    case 0: {
-      constexpr int ZB = 192;  // workgroups of the linearisation launch that clear the system instead
+    case 0:
       if (depth) {
-        const dim3 g(v.M + ZB, v.nch, v.zsplit), b(LIN_THREADS);
-        if (v.wide && v.zsplit > 1)
-          hipLaunchKernelGGL((ba_lin_kernel<true, true, true>), g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
-        else if (v.wide)
-          hipLaunchKernelGGL((ba_lin_kernel<true, true, false>), g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
-        else if (v.zsplit > 1)
-          hipLaunchKernelGGL((ba_lin_kernel<true, false, true>), g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
-        else
-          hipLaunchKernelGGL((ba_lin_kernel<true, false, false>), g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
+        const dim3 g(v.M + plan.zero_wgs, v.nch, v.zsplit), b(LIN_THREADS);
+        const auto lin = v.wide ? (v.zsplit > 1 ? ba_lin_kernel<true, true, true> : ba_lin_kernel<true, true, false>)
+                                : (v.zsplit > 1 ? ba_lin_kernel<true, false, true> : ba_lin_kernel<true, false, false>);
+        hipLaunchKernelGGL(lin, g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
         if (v.zsplit > 1)
           hipLaunchKernelGGL(ba_lin_finish_kernel, dim3(v.M, (v.HW + 255) / 256), dim3(256), 0, s, v, disps, sens, eta);
       } else if (v.E > 0) {
-        hipLaunchKernelGGL((ba_lin_kernel<false, false, false>), dim3(v.E + ZB, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
+        hipLaunchKernelGGL((ba_lin_kernel<false, false, false>), dim3(v.E + plan.zero_wgs, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
                            disps, intr, sens, targets, weights, eta, ii, jj, v.E);
       } else {
         if (v.packed) (void)hipMemsetAsync(v.psys, 0, sizeof(double) * pk_total(v.n), s);
         else (void)hipMemsetAsync(v.sys, 0, sizeof(double) * (size_t)(v.n + 1) * v.ld, s);
       }
       break;
-    }
     case 1:  // (with depth slots the assemble step rides in spare workgroups of the Schur launch, stage 2)
       if (v.E > 0 && !depth)
-        hipLaunchKernelGGL(ba_assemble_kernel, dim3(v.E + (solver_preset_words(v) + 1023) / 1024 + solver_preset_tiles(v)), dim3(64), 0, s, v, poses, ii, jj);
+        hipLaunchKernelGGL(ba_assemble_kernel, dim3(plan.asm_units), dim3(64), 0, s, v, poses, ii, jj);
       break;
     case 2:
       if (depth) {
-        // pixel split so that small graphs still fill the chip (atomics grow with the split)
-        const int tiles = (v.HW + SF_TP - 1) / SF_TP;
-        int nsplit = 1536 / (v.M > 0 ? v.M : 1);
-        nsplit = nsplit < 1 ? 1 : (nsplit > tiles ? tiles : nsplit);
         // dense graphs (mean out-degree >= 12: global BA of a well connected graph, edge-sharded
         // ranks) send their slots of 17..85 entries to the wide kernels
         const int wide = v.wide;
         // sparse slots (<= S2_MAXE edges): Gram tiles per pixel range, then the per-slot fold
-        const int asm_units = v.E > 0 ? v.E + (solver_preset_words(v) + 1023) / 1024 + solver_preset_tiles(v) : 0;
-        const int asm_x = (asm_units + 4 * v.s2_split - 1) / (4 * v.s2_split);  // spare columns of the grid
-        hipLaunchKernelGGL(ba_schur2_kernel, dim3(v.M + asm_x, v.s2_split), dim3(256), 0, s, v, poses, disps, intr, weights, ii, jj,
-                           wide, asm_units);
+        hipLaunchKernelGGL(ba_schur2_kernel, plan.schur2, dim3(256), 0, s, v, poses, disps, intr, weights, ii, jj,
+                           wide, plan.asm_units);
         hipLaunchKernelGGL(ba_schur_fold_kernel, dim3(v.M), dim3(1024), 0, s, v, poses, jj, v.s2_split);
         // slots with more edges than the two kernels above / the SYRK classes below take: block pairs.  Most graphs have
         // none, and the empty launch costs 5 us of every iteration: left out when ba_prep_kernel's hint says so
@@ -2116,23 +2098,16 @@ void launch_build_stage(const BaView& v, const float* poses, const float* disps,
           none3 = tag == v.hint_tag && __atomic_load_n(v.hint + 1, __ATOMIC_RELAXED) == 0;
         }
         if (!none3)
-          hipLaunchKernelGGL(ba_schur_fused_kernel, dim3(v.M, nsplit), dim3(256), 0, s, v, poses, disps,
+          hipLaunchKernelGGL(ba_schur_fused_kernel, dim3(v.M, plan.sf_split), dim3(256), 0, s, v, poses, disps,
                              intr, weights, ii, jj, wide);
         if (wide) {  // dense slots: SYRK straight from the E rows the linearisation wrote (v.Ebuf)
-          hipLaunchKernelGGL((ba_syrk3_kernel<SW_MID, 12, 1, 1, true, true>), dim3(v.M, v.sy_ns[0], 1), dim3(768), 0, s, v);
-          hipLaunchKernelGGL((ba_syrk3_kernel<SW_BIG, 8, 2, 4, false, false>), dim3(v.M, v.sy_ns[1], 4), dim3(512), 0, s, v);
-          hipLaunchKernelGGL(ba_syrk_fold_kernel, dim3(v.M, 34, 2), dim3(256), 0, s, v, v.M * v.sy_ns[0], v.M * v.sy_ns[1]);
+          hipLaunchKernelGGL((ba_syrk3_kernel<SW_MID, 12, 1, 1, true, true>), plan.syrk[0], dim3(768), 0, s, v);
+          hipLaunchKernelGGL((ba_syrk3_kernel<SW_BIG, 8, 2, 4, false, false>), plan.syrk[1], dim3(512), 0, s, v);
+          hipLaunchKernelGGL(ba_syrk_fold_kernel, plan.fold, dim3(256), 0, s, v, v.M * v.sy_ns[0], v.M * v.sy_ns[1]);
         }
       }
       break;
   }
-}
-
-void launch_build(const BaView& v, const float* poses, const float* disps, const float* intr,
-                  const float* sens, const float* targets, const float* weights, const float* eta,
-                  const int64_t* ii, const int64_t* jj, bool motion_only, hipStream_t s) {
-  for (int stage = 0; stage < 3; stage++)
-    launch_build_stage(v, poses, disps, intr, sens, targets, weights, eta, ii, jj, motion_only, stage, s);
 }
 
 void launch_update(const BaView& v, float* poses, float* disps, const float* intr, const float* weights,

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import DroidBackendError  # noqa: F401
+from .ba_binding import BAProblemDev, BaBinding, read_status
 
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
            "altcorr_backward", "corr_index_forward", "corr_index_backward",
@@ -26,37 +27,13 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
-_workspaces = {}   # (device index, stream handle) -> _Workspace
+_workspaces = {}   # (device index, stream handle) -> BaBinding: grow-only scratch of that stream's `ba` calls + status mirror
 
 # Contract violations only a kernel can see (edge index outside the buffer, eta rows != depth slots, a stalled
 # solver grid) are written to a status word.  DROID_HIP_CHECK=1: read it back after every call (one sync) and
 # raise.  Default: no sync -- the last kernel of a call also writes the word to page-locked host memory, and the
 # NEXT `ba` call on the same (device, stream) raises if the previous one had reported a violation by then.
 _SYNC_CHECK = _os.environ.get("DROID_HIP_CHECK", "0") == "1"
-
-
-class _Workspace:
-    """Grow-only scratch of the `ba` calls of one (device, stream) + the host mirror of its status word."""
-
-    def __init__(self):
-        self.buf = None
-        # {status of the last iteration, depth slots, number of iterations that ended with a violation / a stalled
-        # solve so far, OR of their status bits}: written by the device only (include/droid_backends_hip.h)
-        # words 4, 5: launch hints {tag of the call, its slots of Schur class 3}, written by the call's first kernel and read by
-        # the library -- never waited for -- when it enqueues an iteration (droid_ba_attach_launch_hints)
-        self.mirror = torch.zeros(8, dtype=torch.int32).pin_memory()
-        self.seen = 0      # error count already raised / shown to the caller
-
-    def get(self, nbytes, device):
-        if self.buf is None or self.buf.numel() < nbytes:
-            lib = _lib.load()
-            if self.buf is not None:
-                lib.droid_ba_attach_status_mirror(self.buf.data_ptr(), None)
-                lib.droid_ba_attach_launch_hints(self.buf.data_ptr(), None)
-            self.buf = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
-            _lib.check(lib.droid_ba_attach_status_mirror(self.buf.data_ptr(), self.mirror.data_ptr()), "ba (status mirror)")
-            _lib.check(lib.droid_ba_attach_launch_hints(self.buf.data_ptr(), self.mirror.data_ptr() + 16), "ba (launch hints)")
-        return self.buf
 
 
 def _check_input(x, name):
@@ -95,28 +72,19 @@ def _ws_key(device):
 
 def _workspace_obj(device):
     key = _ws_key(device)
-    ws = _workspaces.get(key)
-    if ws is None:
-        ws = _workspaces[key] = _Workspace()
-    return ws
+    return _workspaces.get(key) or _workspaces.setdefault(key, BaBinding())
 
 
 def ba_status(workspace=None):
     """(status, depth_slots) of the last `ba` on the current device and stream (blocking read)."""
-    import ctypes
-    lib = _lib.load()
-    obj = None
-    if workspace is None:
-        dev = torch.cuda.current_device()
-        obj = _workspaces.get((dev, torch.cuda.current_stream(dev).cuda_stream))
-        workspace = obj.buf if obj is not None else None
-    if workspace is None:
+    if workspace is not None:
+        return read_status(_lib.load(), workspace)
+    obj = _workspaces.get(_ws_key(torch.device("cuda")))
+    if obj is None or obj.buf is None:
         return 0, 0
-    st, m = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(lib.droid_ba_status(workspace.data_ptr(), _stream(), ctypes.byref(st), ctypes.byref(m)), "ba_status")
-    if obj is not None:
-        obj.seen = int(obj.mirror[2])   # droid_ba_status synchronised: the caller has seen everything up to here
-    return st.value, m.value
+    st = obj.status()
+    obj.seen = int(obj.mirror[2])   # droid_ba_status synchronised: the caller has seen everything up to here
+    return st
 
 
 _STATUS_TEXT = {1: "edge index outside the pose buffer", 2: "eta rows != number of depth slots "
@@ -141,7 +109,7 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
     one).  eta is not contiguity-checked, as in the reference (droid.cpp:105-112), but it is
     made contiguous here because the kernels index it directly.
     """
-    lib = _lib.load()
+    _lib.load()
     for x, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
                  (intrinsics, "intrinsics"), (disps_sens, "disps_sens"), (ii, "ii"), (jj, "jj")):
         _check_input(x, n)
@@ -151,21 +119,11 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
                  (intrinsics, "intrinsics"), (disps_sens, "disps_sens")):
         if x.dtype != torch.float32:
             raise RuntimeError(f"{n} must be float32")
-    t0, t1, iterations = int(t0), int(t1), int(iterations)
     motion_only = bool(motion_only)
-    nbuf, H, W = disps.shape
-    E = int(ii.shape[0])
-    P = t1 - t0
+    H, W = disps.shape[1:]
     dev = poses.device
-    if motion_only:
-        M = 0
-        eta_c = None
-    else:
-        eta_c = eta.contiguous().to(torch.float32).view(-1, H * W)
-        M = int(eta_c.shape[0])
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, t0, t1, M)
-    if nbytes == 0:
-        raise RuntimeError("droid_backends.ba: bad sizes / window")
+    eta_c = None if motion_only else eta.contiguous().to(torch.float32).view(-1, H * W)
+    p = BAProblemDev(poses, disps, intrinsics, disps_sens, targets, weights, eta_c, ii, jj)
     wso = _workspace_obj(dev)
     # Deferred error report, no sync: the device counts the iterations that ended with a violation or a stalled solve
     # in page-locked host memory and ORs their bits (sticky: a later call cannot overwrite them); raise once per count.
@@ -173,16 +131,12 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
     if nerr != wso.seen:
         wso.seen = nerr
         _raise_on_status(int(wso.mirror[3]) & ~4, int(wso.mirror[1]), " (an earlier call on this stream)")
-    ws = wso.get(nbytes, dev)
-    dx = torch.empty((max(P, 0), 6), dtype=torch.float32, device=dev)
+    E, nbuf, H, W, M, t0, t1 = wso.begin(p, t0, t1, motion_only, dev)
+    dx = torch.empty((max(t1 - t0, 0), 6), dtype=torch.float32, device=dev)
     dz = torch.empty((M, H * W), dtype=torch.float32, device=dev)
-    rc = lib.droid_ba(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), disps_sens.data_ptr(),
-                      _ptr(targets), _ptr(weights), _ptr(eta_c), _ptr(ii), _ptr(jj), E, nbuf, H, W, M,
-                      t0, t1, iterations, float(lm), float(ep), int(motion_only), dx.data_ptr(),
-                      dz.data_ptr() if M > 0 else None, ws.data_ptr(), ws.numel(), _stream())
-    _lib.check(rc, "ba")
+    wso.ba(p, iterations, lm, ep, motion_only, dx, dz)
     if _SYNC_CHECK:
-        st = ba_status(ws)
+        st = wso.status()
         wso.seen = int(wso.mirror[2])
         _raise_on_status(*st)
     return [dx, dz]

@@ -15,26 +15,9 @@ covered by world_size-2 gloo tests on CPU; the product backend is `HipBackend` (
 """
 from __future__ import annotations
 
-import ctypes
-from dataclasses import dataclass
-
 import torch
 
-from . import _lib
-
-
-@dataclass
-class BAProblemDev:
-    """Device tensors of one rank, shaped like the reference's `ba` arguments (droid.cpp:88-102)."""
-    poses: torch.Tensor       # [nbuf,7] f32, replicated on all ranks
-    disps: torch.Tensor       # [nbuf,H,W] f32, valid for owned frames
-    intrinsics: torch.Tensor  # [4]
-    disps_sens: torch.Tensor  # [nbuf,H,W]
-    targets: torch.Tensor     # [E_local,2,H,W]
-    weights: torch.Tensor     # [E_local,2,H,W]
-    eta: torch.Tensor         # [M_local,H,W]  rows = depth slots of THIS rank, ascending frame
-    ii: torch.Tensor          # [E_local] int64
-    jj: torch.Tensor          # [E_local] int64
+from .ba_binding import BAProblemDev, BaBinding  # noqa: F401  (BAProblemDev: the argument of every backend method)
 
 
 def partition_frames(ii, n_frames, world):
@@ -60,90 +43,44 @@ def local_eta_rows(ii_local, t0, t1, own):
 
 
 class HipBackend:
-    """The product compute backend: include/droid_backends_hip.h phase API on the current stream."""
+    """The product compute backend: include/droid_backends_hip.h phase API on the current stream, through BaBinding
+    (launch hints, no status mirror: `status()` reads the workspace)."""
 
     def __init__(self):
-        self.lib = _lib.load()
-        self.ws = None
-        # include/droid_backends_hip.h: launch hints.  One pair of words for the life of the backend: a prepare that is
-        # still queued when the workspace grows writes into them later, so they must outlive every workspace
-        self.hints = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self.binding = BaBinding(status_mirror=False, headroom=(1.0, 4096))
+        self.lib, self.ws = self.binding.lib, None
 
     def __del__(self):
         # the library keys the launch hints by workspace address: drop the registration with the buffers it points to
         try:
-            if self.ws is not None:
-                self.lib.droid_ba_attach_launch_hints(self.ws.data_ptr(), None)
+            self.binding.close()
         except Exception:
             pass
 
-    def _args(self, p: BAProblemDev, t0, t1, motion_only):
-        nbuf, H, W = p.disps.shape
-        E = int(p.ii.shape[0])
-        M = 0 if motion_only else int(p.eta.shape[0])
-        return E, int(nbuf), int(H), int(W), M, int(t0), int(t1)
-
     def prepare(self, p: BAProblemDev, t0, t1, own, motion_only):
-        E, nbuf, H, W, M, t0, t1 = self._args(p, t0, t1, motion_only)
-        nbytes = self.lib.droid_ba_workspace_bytes(E, nbuf, H, W, t0, t1, M)
-        if nbytes == 0:
-            raise RuntimeError("ba: bad sizes / window")
-        if self.ws is None or self.ws.numel() < nbytes:
-            if self.ws is not None:
-                self.lib.droid_ba_attach_launch_hints(self.ws.data_ptr(), None)
-            self.ws = torch.empty(nbytes + 4096, dtype=torch.uint8, device=p.poses.device)
-            _lib.check(self.lib.droid_ba_attach_launch_hints(self.ws.data_ptr(), self.hints.data_ptr()), "ba (launch hints)")
-        self._dims = (E, nbuf, H, W, M, t0, t1)
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.droid_ba_prepare(p.ii.data_ptr(), p.jj.data_ptr(), E, nbuf, H, W, M, t0, t1,
-                                             int(own[0]), int(own[1]), int(motion_only), self.ws.data_ptr(),
-                                             self.ws.numel(), s), "ba_prepare")
-        nel_sys = ctypes.c_size_t(0)
-        ptr = self.lib.droid_ba_system(self.ws.data_ptr(), E, nbuf, H, W, t0, t1, M, ctypes.byref(nel_sys))
-        off = ptr - self.ws.data_ptr()
-        self.system = self.ws[off:off + nel_sys.value * 8].view(torch.float64)
-        nel = ctypes.c_size_t(0)
-        ptr = self.lib.droid_ba_packed_system(self.ws.data_ptr(), E, nbuf, H, W, t0, t1, M, ctypes.byref(nel))
-        off = ptr - self.ws.data_ptr()
-        self.packed = self.ws[off:off + nel.value * 8].view(torch.float64)   # lower triangle + rhs row, contiguous
+        b = self.binding
+        E, nbuf, H, W, M, t0, t1 = b.begin(p, t0, t1, motion_only, p.poses.device)
+        self.ws = b.buf
+        b.prepare(p, own, motion_only)
+        self.system = b.system()
+        self.packed = b.packed()   # lower triangle + rhs row, contiguous
         self.dx = torch.empty((t1 - t0, 6), dtype=torch.float32, device=p.poses.device)
         self.dz = torch.empty((M, H * W), dtype=torch.float32, device=p.poses.device)
 
     def build(self, p: BAProblemDev, motion_only):
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.droid_ba_build(p.poses.data_ptr(), p.disps.data_ptr(), p.intrinsics.data_ptr(),
-                                           p.disps_sens.data_ptr(), p.targets.data_ptr(), p.weights.data_ptr(),
-                                           p.eta.data_ptr() if M > 0 else None, p.ii.data_ptr(), p.jj.data_ptr(),
-                                           E, nbuf, H, W, M, t0, t1, int(motion_only), self.ws.data_ptr(),
-                                           self.ws.numel(), s), "ba_build")
+        self.binding.build(p, motion_only)
         return self.system
 
     def build_packed(self, p: BAProblemDev, motion_only):
         """Multi-GPU build phase: the contribution of this rank lands in `self.packed` (what gets all-reduced)."""
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.droid_ba_build_packed(p.poses.data_ptr(), p.disps.data_ptr(), p.intrinsics.data_ptr(),
-                                                  p.disps_sens.data_ptr(), p.targets.data_ptr(), p.weights.data_ptr(),
-                                                  p.eta.data_ptr() if M > 0 else None, p.ii.data_ptr(), p.jj.data_ptr(),
-                                                  E, nbuf, H, W, M, t0, t1, int(motion_only), self.ws.data_ptr(),
-                                                  self.ws.numel(), s), "ba_build_packed")
+        self.binding.build(p, motion_only, packed=True)
         return self.packed
 
     def unpack(self, motion_only):
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        _lib.check(self.lib.droid_ba_unpack_system(E, nbuf, H, W, M, t0, t1, int(motion_only), self.ws.data_ptr(),
-                                                   self.ws.numel(), torch.cuda.current_stream().cuda_stream),
-                   "ba_unpack_system")
+        self.binding.unpack_system(motion_only)
 
     def solve_update(self, p: BAProblemDev, lm, ep, motion_only):
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.droid_ba_solve_update(p.poses.data_ptr(), p.disps.data_ptr(), p.intrinsics.data_ptr(),
-                                                  p.weights.data_ptr(), p.ii.data_ptr(), p.jj.data_ptr(), E, nbuf, H, W, M, t0, t1, float(lm), float(ep),
-                                                  int(motion_only), self.dx.data_ptr(),
-                                                  self.dz.data_ptr() if M > 0 else None, self.ws.data_ptr(),
-                                                  self.ws.numel(), s), "ba_solve_update")
+        self.binding.solve_update(p, lm, ep, motion_only, self.dx, self.dz)
         return self.dx
 
     # ---- overlap of the collective with the solve (opt-in: ShardedBA(overlap=True)) ----------------------------
@@ -152,53 +89,25 @@ class HipBackend:
 
     def overlap_plan(self):
         """[(first, last)] element ranges of `self.packed`, one per chunk (whole block rows of the system, in order)."""
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        nc = ctypes.c_int(0)
-        offs = (ctypes.c_size_t * (self.OVERLAP_MAX_CHUNKS + 1))()
-        _lib.check(self.lib.droid_ba_overlap_plan(t0, t1, self.OVERLAP_MAX_CHUNKS, ctypes.byref(nc), offs), "ba_overlap_plan")
-        return [(int(offs[c]), int(offs[c + 1])) for c in range(nc.value)]
+        return self.binding.overlap_plan(self.OVERLAP_MAX_CHUNKS)
 
     def unpack_chunk(self, chunk, lm, ep, epoch):
         """Chunk `chunk` of the (all-reduced) packed system -> pitched matrix, damped, then published for `epoch`;
         on the current stream (the side stream of the overlap)."""
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        _lib.check(self.lib.droid_ba_unpack_chunk(E, nbuf, H, W, M, t0, t1, int(chunk), self.OVERLAP_MAX_CHUNKS, float(lm),
-                                                  float(ep), int(epoch), self.ws.data_ptr(), self.ws.numel(),
-                                                  torch.cuda.current_stream().cuda_stream), "ba_unpack_chunk")
+        self.binding.unpack_chunk(chunk, self.OVERLAP_MAX_CHUNKS, lm, ep, epoch)
 
     def solve_update_overlap(self, p: BAProblemDev, epoch, motion_only):
         """Launches the solve of iteration `epoch` BEFORE its system has been reduced: the factorisation waits for the
         block rows it is about to read.  Returns False when the single-launch solver cannot take this system."""
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        s = torch.cuda.current_stream().cuda_stream
-        rc = self.lib.droid_ba_solve_update_overlap(p.poses.data_ptr(), p.disps.data_ptr(), p.intrinsics.data_ptr(),
-                                                    p.weights.data_ptr(), p.ii.data_ptr(), p.jj.data_ptr(), E, nbuf, H, W, M,
-                                                    t0, t1, int(epoch), int(motion_only), self.dx.data_ptr(),
-                                                    self.dz.data_ptr() if M > 0 else None, self.ws.data_ptr(),
-                                                    self.ws.numel(), s)
-        if rc == -1:      # DROID_E_ARG: not available for this system
-            return False
-        _lib.check(rc, "ba_solve_update_overlap")
-        return True
+        return self.binding.solve_update_overlap(p, epoch, motion_only, self.dx, self.dz)
 
     def profile_iteration(self, p: BAProblemDev, lm, ep, motion_only):
         """Stage times in ms of one iteration (measurement support, synchronises)."""
-        E, nbuf, H, W, M, t0, t1 = self._dims
-        ms = (ctypes.c_float * 8)()
-        s = torch.cuda.current_stream().cuda_stream
-        _lib.check(self.lib.droid_ba_profile_iteration(
-            p.poses.data_ptr(), p.disps.data_ptr(), p.intrinsics.data_ptr(), p.disps_sens.data_ptr(),
-            p.targets.data_ptr(), p.weights.data_ptr(), p.eta.data_ptr() if M > 0 else None, p.ii.data_ptr(),
-            p.jj.data_ptr(), E, nbuf, H, W, M, t0, t1, float(lm), float(ep), int(motion_only),
-            self.ws.data_ptr(), self.ws.numel(), s, ms), "ba_profile_iteration")
         names = ["linearize", "assemble", "schur", "unused", "factor", "backsolve", "update", "total"]
-        return dict(zip(names, [float(x) for x in ms]))
+        return dict(zip(names, self.binding.profile_iteration(p, lm, ep, motion_only)))
 
     def status(self):
-        st, m = ctypes.c_int(0), ctypes.c_int(0)
-        _lib.check(self.lib.droid_ba_status(self.ws.data_ptr(), torch.cuda.current_stream().cuda_stream,
-                                            ctypes.byref(st), ctypes.byref(m)), "ba_status")
-        return st.value, m.value
+        return self.binding.status()
 
 
 class ShardedBA:

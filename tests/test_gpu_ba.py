@@ -112,30 +112,19 @@ def test_chol_failure_flag_single_launch(backends):
 def test_reduced_system_matches_oracle(backends, oracle, synth):
     """Phase API: the dense (A - S | b) the device builds equals the oracle's, entry by entry."""
     torch = _torch()
-    import ctypes
-    lib = backends._lib.load()
+    from droid_backends.ba_binding import BAProblemDev, BaBinding
     p = synth.make_config("cfg1")
     ref = oracle.ba(*ba_args(p), 1, p.lm, p.ep, False, debug=True)
-    d = to_dev(p, torch)
-    nbuf, H, W = p.disps.shape
-    E, M, P = len(p.ii), p.eta.shape[0], p.t1 - p.t0
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, M)
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    rc = lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, M, p.t0, p.t1, 0, nbuf, 0,
-                              ws.data_ptr(), nbytes, s)
-    assert rc == 0
-    rc = lib.droid_ba_build(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                            d["disps_sens"].data_ptr(), d["targets"].data_ptr(), d["weights"].data_ptr(),
-                            d["eta"].data_ptr(), d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, M,
-                            p.t0, p.t1, 0, ws.data_ptr(), nbytes, s)
-    assert rc == 0
+    d = BAProblemDev(**to_dev(p, torch))
+    b = BaBinding(status_mirror=False, headroom=(1, 0))
+    b.begin(d, p.t0, p.t1, False)
+    b.buf.zero_()
+    b.prepare(d, (0, p.disps.shape[0]), False)
+    b.build(d, False)
     torch.cuda.synchronize()
-    nel = ctypes.c_size_t(0)
-    ptr = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, M, ctypes.byref(nel))
-    off = ptr - ws.data_ptr()
-    n = 6 * P
-    sys_ = ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, -1).cpu().numpy()
+    n = 6 * (p.t1 - p.t0)
+    sys_ = b.system().view(n + 1, -1).cpu().numpy()
+    b.close()
     Hd = np.tril(sys_[:n, :n])
     Ho = np.tril(ref["H"])
     scale = np.abs(Ho).max()
@@ -153,6 +142,26 @@ def test_ba_cfg1_mono(backends, oracle, synth, iterations):
 def test_ba_tiny_3kf_4e(backends, oracle, synth):
     p = synth.make_ba_problem(N=3, E=4, H=16, W=24, seed=11)
     _check(backends, oracle, p, 2, tag="3kf/4e")
+
+
+def test_ba_grown_workspace_keeps_its_pinned_words(backends, oracle, synth):
+    """One stream, two calls: the 3-keyframe graph, then a graph with a slot in every Schur class that needs a larger
+    workspace.  The second call is at parity, the status is clean, and the stream still has ONE entry in `_workspaces`
+    whose pinned words (status mirror + launch hints) are the tensor it had before the workspace grew."""
+    torch = _torch()
+    from stage_graphs import every_class
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        _check(backends, oracle, synth.make_ba_problem(N=3, E=4, H=16, W=24, seed=11), 2, tag="3kf/4e on a fresh stream")
+        w = backends._workspaces[(torch.cuda.current_device(), s.cuda_stream)]
+        words, words_ptr, buf0, bytes0 = w.mirror, w.mirror.data_ptr(), w.buf.data_ptr(), w.buf.numel()
+        _check(backends, oracle, every_class(synth), 1, tag="every class, grown workspace")
+        assert backends.ba_status()[0] & 15 == 0
+    keys = [k for k in backends._workspaces if k[1] == s.cuda_stream]
+    assert len(keys) == 1 and backends._workspaces[keys[0]] is w
+    assert w.buf.numel() > bytes0 and w.buf.data_ptr() != buf0      # it did grow
+    assert w.mirror is words and w.mirror.data_ptr() == words_ptr and words.is_pinned()
+    assert int(words[w.HINT_WORD]) >= 1 and int(words[w.HINT_WORD + 1]) > 0   # the hint of the second call: class-3 slots
 
 
 def test_ba_rgbd_sensor_depth(backends, oracle, synth):

@@ -7,7 +7,6 @@
   droid_ba_build left in the workspace (motion-only problem with P window frames, so 6P + 1 crosses the 16-double pitch
   and the 64-column tile boundaries) and droid_ba_solve_update's dx is held to float32 of the longdouble solve of the
   damped matrix."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -89,21 +88,16 @@ def test_damped_solve_of_an_injected_system(backends, synth, P):
     damped wrongly does, by an amount that follows (lm, ep) and vanishes at (0, 0): the undamped call tells the two
     apart, and the padding is looked at directly."""
     torch = _torch()
-    lib = backends._lib.load()
+    from droid_backends.ba_binding import BAProblemDev, BaBinding
     p = _motion_problem(synth, P)
-    d = to_dev(p, torch)
-    nbuf, H, W = p.disps.shape
-    E, n = len(p.ii), 6 * P
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, 0)
-    assert nbytes > 0
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    nel = ctypes.c_size_t(0)
-    ptr = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, 0, ctypes.byref(nel))
-    off = ptr - ws.data_ptr()
+    d = BAProblemDev(**to_dev(p, torch))
+    nbuf, n = p.disps.shape[0], 6 * P
+    bd = BaBinding(status_mirror=False, headroom=(1, 0))
+    bd.begin(d, p.t0, p.t1, True)
+    bd.buf.zero_()
     ld = (n + 1 + 15) // 16 * 16
-    assert nel.value == (n + 1) * ld
-    sysv = ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, ld)
+    assert bd.system().numel() == (n + 1) * ld
+    sysv = bd.system().view(n + 1, ld)
     rng = np.random.default_rng(P)
     A = 1e4 * C.spectrum_matrix(rng, n, np.logspace(0, -6, n))          # diagonal ~ 1e3, kappa 1e6 undamped
     b = rng.normal(size=n)
@@ -112,26 +106,19 @@ def test_damped_solve_of_an_injected_system(backends, synth, P):
     host[:n, :n] = np.tril(A)
     host[n, :n] = b
     host[n, n] = CORNER      # the rhs row's own "diagonal" entry: a damping loop one row too long would change it
-    poses0 = d["poses"].clone()
+    poses0 = d.poses.clone()
     failures = []
     corner0 = None
     for lm, ep in ((0.0, 0.0), (1e-4, 0.1), (1e-2, 1e-6)):
-        d["poses"].copy_(poses0)
-        assert lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, 0, p.t0, p.t1, 0, nbuf, 1,
-                                    ws.data_ptr(), nbytes, s) == 0
-        assert lib.droid_ba_build(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                                  d["disps_sens"].data_ptr(), d["targets"].data_ptr(), d["weights"].data_ptr(), None,
-                                  d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, 0, p.t0, p.t1, 1,
-                                  ws.data_ptr(), nbytes, s) == 0
+        d.poses.copy_(poses0)
+        bd.prepare(d, (0, nbuf), True)
+        bd.build(d, True)
         sysv.copy_(torch.from_numpy(host))
         dx = torch.full((P, 6), float("nan"), dtype=torch.float32, device="cuda")
-        assert lib.droid_ba_solve_update(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                                         d["weights"].data_ptr(), d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W,
-                                         0, p.t0, p.t1, lm, ep, 1, dx.data_ptr(), None, ws.data_ptr(), nbytes, s) == 0
+        bd.solve_update(d, lm, ep, True, dx, None)
         torch.cuda.synchronize()
-        st, m = ctypes.c_int(0), ctypes.c_int(0)
-        assert lib.droid_ba_status(ws.data_ptr(), s, ctypes.byref(st), ctypes.byref(m)) == 0
-        assert st.value == 0, st.value
+        st, m = bd.status()
+        assert st == 0, st
         Ad = C.damp(A, lm, ep)
         xref, errs = R.cpu_yardstick(Ad, b)
         bar_f = R.bars(errs, (C.SPREAD_FWD, C.SPREAD_OMEGA))[0]
@@ -156,4 +143,5 @@ def test_damped_solve_of_an_injected_system(backends, synth, P):
             failures.append((lm, ep, f"S[n, n] = {corner!r}, the undamped run left {corner0!r}: the rhs row was damped"))
         if pad_damped:
             failures.append((lm, ep, "the padding columns hold the damping constant"))
+    bd.close()
     assert not failures, failures

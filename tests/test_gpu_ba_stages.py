@@ -84,7 +84,6 @@ def test_launch_hint_after_workspace_growth_is_not_stale(backends, oracle, synth
     import copy
     torch = _torch()
     from util import ba_args, compare_state, run_hip_ba, to_dev
-    lib = backends._lib.load()
     small = synth.make_ba_problem(N=5, E=14, H=24, W=32, seed=1)    # 2.3 MB of workspace, the graph below needs 12 MB
     big = GRAPHS["dense30_block_pair"][0](synth)
     s = torch.cuda.Stream()
@@ -104,11 +103,11 @@ def test_launch_hint_after_workspace_growth_is_not_stale(backends, oracle, synth
         assert backends.ba_status()[0] & 11 == 0
         assert int(w.mirror[5]) > 0              # the hint of this call has arrived by now and names class-3 slots
         hip = dict(poses=d["poses"].cpu().numpy(), disps=d["disps"].cpu().numpy(), dx=np.zeros(0))
-        lib.droid_ba_attach_launch_hints(w.buf.data_ptr(), None)
+        w.attach_hints(False)
         try:
             ref_dev = run_hip_ba(backends, copy.deepcopy(big), torch, 1)   # every launch made
         finally:
-            lib.droid_ba_attach_launch_hints(w.buf.data_ptr(), w.mirror.data_ptr() + 16)
+            w.attach_hints()
     ref = oracle.ba(*ba_args(big), 1, big.lm, big.ep, False, storage_f32=True)
     et, er, ed = compare_state(hip, ref, "grown workspace, stream held")
     dev_p, dev_d = np.abs(hip["poses"] - ref_dev["poses"]).max(), np.abs(hip["disps"] - ref_dev["disps"]).max()

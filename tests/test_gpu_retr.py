@@ -17,7 +17,6 @@ Measured on the MI355X, worst over the four start sets and the |tau| classes (fl
           2 pi+0.1  4.3  / 4.6     4.0  / 2.8
 The float32 oracle's error is floored at 1 unit (the rounding of the output) before the factor 4: a class holds
 three draws, and 4 x a lucky 0 would demand bit equality with fp64."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -64,42 +63,32 @@ def test_retraction_of_a_prescribed_xi(backends, oracle, kind):
     import torch
     from droid_backends import synth
     assert torch.cuda.is_available()
-    lib = backends._lib.load()
+    from droid_backends.ba_binding import BAProblemDev, BaBinding
     rng = np.random.default_rng(31)
     k = np.arange(P)
     p = synth.make_ba_problem(N=P + 1, H=16, W=24, seed=17, edges=(np.concatenate([k, k + 1]), np.concatenate([k + 1, k])))
     assert p.t0 == 1 and p.t1 - p.t0 == P
     xi, cls = xi_classes(rng)
     p.poses = start_poses(kind, p, rng)
-    d = to_dev(p, torch)
-    nbuf, H, W = p.disps.shape
-    E, n = len(p.ii), 6 * P
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, 0)
-    assert nbytes > 0
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    d = BAProblemDev(**to_dev(p, torch))
+    n = 6 * P
+    b = BaBinding(status_mirror=False, headroom=(1, 0))
+    b.begin(d, p.t0, p.t1, True)
+    b.buf.zero_()
     dx = torch.zeros((P, 6), dtype=torch.float32, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    assert lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, 0, p.t0, p.t1, 0, nbuf, 1,
-                                ws.data_ptr(), nbytes, s) == 0
-    assert lib.droid_ba_build(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                              d["disps_sens"].data_ptr(), d["targets"].data_ptr(), d["weights"].data_ptr(), None,
-                              d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, 0, p.t0, p.t1, 1, ws.data_ptr(),
-                              nbytes, s) == 0
-    nel = ctypes.c_size_t(0)
-    off = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, 0, ctypes.byref(nel)) - ws.data_ptr()
-    system = ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, -1)
+    b.prepare(d, (0, p.disps.shape[0]), True)
+    b.build(d, True)
+    system = b.system().view(n + 1, -1)
     system.zero_()
     system[:n, :n] = torch.eye(n, dtype=torch.float64, device="cuda")
     system[n, :n] = torch.from_numpy(xi.reshape(-1).astype(np.float64)).cuda()
-    assert lib.droid_ba_solve_update(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                                     d["weights"].data_ptr(), d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, 0,
-                                     p.t0, p.t1, 0.0, 0.0, 1, dx.data_ptr(), None, ws.data_ptr(), nbytes, s) == 0
+    b.solve_update(d, 0.0, 0.0, True, dx, None)
     torch.cuda.synchronize()
-    st, m = ctypes.c_int(0), ctypes.c_int(0)
-    assert lib.droid_ba_status(ws.data_ptr(), s, ctypes.byref(st), ctypes.byref(m)) == 0
-    assert st.value == 0, st.value
+    st, m = b.status()
+    b.close()
+    assert st == 0, st
     assert np.array_equal(dx.cpu().numpy().view(np.uint32), xi.view(np.uint32))          # bit for bit
-    got = d["poses"].cpu().numpy()
+    got = d.poses.cpu().numpy()
     assert np.array_equal(got[0], p.poses[0])                                            # frame 0 is not in the window
     units = {}
     for r in range(P):

@@ -226,7 +226,6 @@ def test_launch_hints_name_the_block_pair_class_and_do_not_change_results(backen
     import droid_backends as db
     from droid_backends import synth
     from util import run_hip_ba
-    lib = db._lib.load()
     key = (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream)
     for p, expect_slots in ((synth.make_config("cfg2"), False),
                             (synth.make_ba_problem(N=30, E=720, H=15, W=20, seed=78, lm=1e-4, ep=0.1), True)):
@@ -235,8 +234,8 @@ def test_launch_hints_name_the_block_pair_class_and_do_not_change_results(backen
         tag0 = int(w.mirror[4])
         assert tag0 >= 1                                            # the hint of the call has arrived
         assert (int(w.mirror[5]) > 0) == expect_slots, (int(w.mirror[5]), expect_slots)
-        lib.droid_ba_attach_launch_hints(w.buf.data_ptr(), None)
+        w.attach_hints(False)
         b = run_hip_ba(backends, copy.deepcopy(p), torch, 4)
         assert int(w.mirror[4]) == tag0                             # detached: not written
-        lib.droid_ba_attach_launch_hints(w.buf.data_ptr(), w.mirror.data_ptr() + 16)
+        w.attach_hints()
         assert np.abs(a["poses"] - b["poses"]).max() < 1e-6 and np.abs(a["disps"] - b["disps"]).max() < 1e-6

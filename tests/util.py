@@ -178,57 +178,36 @@ def damped_solve(H, b, lm, ep):
 
 
 def run_ba_stages(backends, p, torch, motion_only=False, packed=False):
-    """One Gauss-Newton iteration through the phase ABI on a workspace of its own, with launch hints of its own:
-    droid_ba_prepare, droid_ba_build (its system copied before the solve factors it in place), optionally
+    """One Gauss-Newton iteration through the phase ABI on a workspace of its own, with launch hints of its own (a
+    BaBinding): droid_ba_prepare, droid_ba_build (its system copied before the solve factors it in place), optionally
     droid_ba_build_packed + droid_ba_unpack_system (copied too), droid_ba_solve_update.  Returns the copies, the
     state after the update, dx, the header words and the hint words {tag, slots of Schur class 3}."""
-    import ctypes
-    lib = backends._lib.load()
-    d = to_dev(p, torch)
-    nbuf, H, W = p.disps.shape
-    E, P = len(p.ii), p.t1 - p.t0
-    M = 0 if motion_only else p.eta.shape[0]
-    n = 6 * P
-    eta = None if motion_only else d["eta"].data_ptr()
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, M)
-    assert nbytes > 0
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    hints = torch.zeros(2, dtype=torch.int32).pin_memory()
-    dx = torch.zeros((P, 6), dtype=torch.float32, device="cuda")
+    from droid_backends.ba_binding import BAProblemDev, BaBinding
+    d = BAProblemDev(**to_dev(p, torch))
+    b = BaBinding(status_mirror=False, headroom=(1, 0))     # a zeroed workspace of exactly the size asked for
+    E, nbuf, H, W, M, t0, t1 = b.begin(d, p.t0, p.t1, motion_only)
+    b.buf.zero_()
+    n = 6 * (t1 - t0)
+    dx = torch.zeros((t1 - t0, 6), dtype=torch.float32, device="cuda")
     dz = torch.zeros((max(M, 1), H * W), dtype=torch.float32, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    args = (d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(), d["disps_sens"].data_ptr(),
-            d["targets"].data_ptr(), d["weights"].data_ptr(), eta, d["ii"].data_ptr(), d["jj"].data_ptr(),
-            E, nbuf, H, W, M, p.t0, p.t1, int(motion_only), ws.data_ptr(), nbytes, s)
-    nel = ctypes.c_size_t(0)
-    ptr = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, M, ctypes.byref(nel))
-    off = ptr - ws.data_ptr()
-    system = lambda: ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, -1)[:, :n].cpu().numpy().copy()
-    assert lib.droid_ba_attach_launch_hints(ws.data_ptr(), hints.data_ptr()) == 0
+    system = lambda: b.system().view(n + 1, -1)[:, :n].cpu().numpy().copy()
     try:
-        assert lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, M, p.t0, p.t1, 0, nbuf,
-                                    int(motion_only), ws.data_ptr(), nbytes, s) == 0
-        assert lib.droid_ba_build(*args) == 0
+        b.prepare(d, (0, nbuf), motion_only)
+        b.build(d, motion_only)
         torch.cuda.synchronize()
-        hdr = ws[:64].view(torch.int32).cpu().numpy().copy()
-        out = dict(system=system(), hdr=hdr, hint=(int(hints[0]), int(hints[1])))
+        hw = b.HINT_WORD
+        out = dict(system=system(), hdr=b.header(), hint=(int(b.mirror[hw]), int(b.mirror[hw + 1])))
         if packed:
-            assert lib.droid_ba_build_packed(*args) == 0
-            assert lib.droid_ba_unpack_system(E, nbuf, H, W, M, p.t0, p.t1, int(motion_only), ws.data_ptr(), nbytes,
-                                              s) == 0
+            b.build(d, motion_only, packed=True)
+            b.unpack_system(motion_only)
             torch.cuda.synchronize()
             out["system_packed"] = system()
-        assert lib.droid_ba_solve_update(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                                         d["weights"].data_ptr(), d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W,
-                                         M, p.t0, p.t1, float(p.lm), float(p.ep), int(motion_only), dx.data_ptr(),
-                                         dz.data_ptr() if M > 0 else None, ws.data_ptr(), nbytes, s) == 0
+        b.solve_update(d, p.lm, p.ep, motion_only, dx, dz)
         torch.cuda.synchronize()
-        st, m = ctypes.c_int(0), ctypes.c_int(0)
-        assert lib.droid_ba_status(ws.data_ptr(), s, ctypes.byref(st), ctypes.byref(m)) == 0
+        st, m = b.status()
     finally:
-        lib.droid_ba_attach_launch_hints(ws.data_ptr(), None)
-    out.update(status=st.value, M=m.value, dx=dx.cpu().numpy(), poses=d["poses"].cpu().numpy(),
-               disps=d["disps"].cpu().numpy())
+        b.close()
+    out.update(status=st, M=m, dx=dx.cpu().numpy(), poses=d.poses.cpu().numpy(), disps=d.disps.cpu().numpy())
     return out
 
 

@@ -4,7 +4,6 @@ device (phase API) with and without the Schur part, compares A = sum of Hessian 
 against the fp64 oracle's, and propagates each difference through the damped solve in numpy:
     dx(H, b) = (H + diag(ep + lm diag H))^-1 b
 Not a test; the oracle is used as the checker only.  usage: python tools/noise_probe.py [seed] [config]"""
-import ctypes
 import os
 import sys
 
@@ -16,12 +15,11 @@ import torch
 import droid_backends as db
 import oracle
 from droid_backends import synth
-from util import ba_args, to_dev
+from util import ba_args, run_ba_stages, to_dev
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 12
 cfg = sys.argv[2] if len(sys.argv) > 2 else "cfg3"      # e.g. `noise_probe.py 3 cfg4`: the dense-slot path
 p = synth.make_config(cfg, seed=seed)
-lib = db._lib.load()
 nbuf, H, W = p.disps.shape
 E, M, P = len(p.ii), p.eta.shape[0], p.t1 - p.t0
 n = 6 * P
@@ -29,22 +27,7 @@ ref = oracle.ba(*ba_args(p), 1, p.lm, p.ep, False, debug=True)
 
 
 def device_system(motion_only):
-    d = to_dev(p, torch)
-    m = 0 if motion_only else M
-    nbytes = lib.droid_ba_workspace_bytes(E, nbuf, H, W, p.t0, p.t1, m)
-    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    assert lib.droid_ba_prepare(d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, m, p.t0, p.t1, 0, nbuf,
-                                int(motion_only), ws.data_ptr(), nbytes, s) == 0
-    assert lib.droid_ba_build(d["poses"].data_ptr(), d["disps"].data_ptr(), d["intrinsics"].data_ptr(),
-                              d["disps_sens"].data_ptr(), d["targets"].data_ptr(), d["weights"].data_ptr(),
-                              d["eta"].data_ptr() if m else None, d["ii"].data_ptr(), d["jj"].data_ptr(), E, nbuf, H, W, m,
-                              p.t0, p.t1, int(motion_only), ws.data_ptr(), nbytes, s) == 0
-    torch.cuda.synchronize()
-    nel = ctypes.c_size_t(0)
-    ptr = lib.droid_ba_system(ws.data_ptr(), E, nbuf, H, W, p.t0, p.t1, m, ctypes.byref(nel))
-    off = ptr - ws.data_ptr()
-    sy = ws[off:off + nel.value * 8].view(torch.float64).view(n + 1, -1).cpu().numpy()
+    sy = run_ba_stages(db, p, torch, motion_only)["system"]   # the system droid_ba_build left, before the solve
     L = np.tril(sy[:n, :n])
     return L + np.tril(L, -1).T, sy[n, :n].copy()
 
