@@ -49,6 +49,9 @@ void launch_iproj(const float* poses, const float* disps, const float* intr, int
 void launch_depth_filter(const float* poses, const float* disps, const float* intr,
                          const int64_t* ix, const float* thresh, int num, int nbuf, int H, int W,
                          float* counter, hipStream_t s);
+// upsample.hip
+void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
+                         bool half_mask, hipStream_t s);
 // chol.hip
 void launch_chol_pack(const double* A, const double* b, double* S, int n, int ld, hipStream_t s);
 void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
@@ -630,6 +633,24 @@ int droid_depth_filter(const float* poses, const float* disps, const float* intr
   if (!poses || !disps || !intrinsics || !ix || !thresh || !counter) return fail(DROID_E_ARG, "depth_filter: null %s", "pointer");
   launch_depth_filter(poses, disps, intrinsics, ix, thresh, num, nbuf, H, W, counter, (hipStream_t)stream);
   return check_hip("depth_filter");
+}
+
+// ---------------------------------------------------------------------------- convex upsampling
+int droid_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf_in,
+                       int nbuf_out, int H, int W, int mask_dtype, void* stream) {
+  if (mask_dtype != DROID_F16 && mask_dtype != DROID_F32) return fail(DROID_E_ARG, "cvx_upsample: bad %s", "mask dtype (f16 or f32)");
+  if (H < 1 || W < 1) return fail(DROID_E_ARG, "cvx_upsample: bad %s", "map size (H, W >= 1)");
+  if (n < 0) return fail(DROID_E_ARG, "cvx_upsample: bad %s", "n (negative)");
+  if (nbuf_in < 1 || nbuf_out < 1) return fail(DROID_E_ARG, "cvx_upsample: bad %s", "nbuf_in / nbuf_out (at least 1)");
+  // the kernel keeps a coarse pixel index in 32 bits and element offsets in 64
+  const unsigned __int128 hw = (unsigned __int128)H * W, lim = (unsigned __int128)1 << 62;
+  if (hw > 0x7fffffffu - 64 || 64 * hw * nbuf_out > lim || 576 * hw * (n > 0 ? n : 1) > lim)
+    return fail(DROID_E_ARG, "cvx_upsample: %s", "8H * 8W * nbuf_out (or the mask) exceeds the kernel's index range");
+  if (n == 0) return DROID_OK;
+  if (!data || !mask || !out) return fail(DROID_E_ARG, "cvx_upsample: null %s", "pointer");
+  launch_cvx_upsample(data, ix, mask, out, n, nbuf_in < nbuf_out ? nbuf_in : nbuf_out, H, W, mask_dtype == DROID_F16,
+                      (hipStream_t)stream);
+  return check_hip("cvx_upsample");
 }
 
 // ---------------------------------------------------------------------------- factor-graph edge selection

@@ -23,7 +23,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "altcorr_pyramid_forward", "reproject", "motion_features", "frame_distance_matrix",
            "corr_pyramid_forward",  # the last four are additions
            "proximity_edges",       # add_proximity_factors' edge selection, on the device
-           "corr_volume_pyramid"]   # CorrBlock.__init__ for a list of edges, in one launch
+           "corr_volume_pyramid",   # CorrBlock.__init__ for a list of edges, in one launch
+           "upsample_disps", "cvx_upsample"]   # DepthVideo.upsample / droid_net.cvx_upsample, in one launch
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
@@ -341,6 +342,78 @@ def iproj(poses, disps, intrinsics):
     _lib.check(lib.droid_iproj(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), nm, H, W,
                                points.data_ptr(), _stream()), "iproj")
     return points
+
+
+def _upsample_args(what, mask, n, h, w, f32, ix=None):
+    """Checks of a convex upsampling, shapes and dtypes before devices so that a caller's mistake is named as what it
+    is: f32 = ((tensor, name), ...) must be contiguous float32; the mask is returned as [n, 576, h, w], half or fp32
+    (droid_cvx_upsample); every tensor must be on one HIP device."""
+    for x, name in f32:
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"{what}: {name} must be float32, got {x.dtype}")
+    if ix is not None and ix.dtype != torch.int64:
+        raise RuntimeError(f"{what}: ix must be int64 (torch.long), got {ix.dtype}")
+    if mask.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{what}: mask must be float16 or float32, got {mask.dtype}")
+    for x, name in f32 + ((mask, "mask"),) + (((ix, "ix"),) if ix is not None else ()):
+        if not x.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be contiguous")
+    if mask.dim() == 5 and mask.shape[0] == 1:
+        mask = mask[0]
+    if mask.dim() != 4 or mask.shape[-3] != 576:
+        raise RuntimeError(f"{what}: mask must be [1, n, 576, h, w] or [n, 576, h, w] (9 taps x 8 x 8 sub-pixels), got "
+                           f"{tuple(mask.shape)}")
+    if tuple(mask.shape) != (n, 576, h, w):
+        raise RuntimeError(f"{what}: mask must be [{n}, 576, {h}, {w}] for {n} frames of {h} x {w}, got {tuple(mask.shape)}")
+    for x, name in f32 + ((mask, "mask"),) + (((ix, "ix"),) if ix is not None else ()):
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
+        if x.device != mask.device:
+            raise RuntimeError(f"{what}: {name} is on {x.device}, the mask on {mask.device}")
+    return mask
+
+
+def upsample_disps(disps, ix, mask, out):
+    """The body of `DepthVideo.upsample` (droid_slam/depth_video.py:134-138) in one launch:
+    out[ix] = cvx_upsample(disps[ix].unsqueeze(-1), mask).squeeze(-1), without the gathered copy, the fp32 product
+    [n, 1, 9, 8, 8, h, w], the permuted copy and the index_put.  disps [buffer, h, w] float32 (only read); ix [n] int64
+    on the device, pairwise distinct; mask [1, n, 576, h, w] or [n, 576, h, w], float16 or float32 (the update
+    operator's `upmask`); out [buffer, 8h, 8w] float32, written in place at the frames ix and returned.  A frame index
+    outside both buffers is skipped.  The softmax weights stay fp32 (the stock chain rounds them to half for a half
+    mask).  Never synchronises; no autograd.  Contract: include/droid_backends_hip.h (droid_cvx_upsample).  An addition."""
+    lib = _lib.load()
+    if disps.dim() != 3 or out.dim() != 3 or ix.dim() != 1:
+        raise RuntimeError("upsample_disps: disps must be [buffer, h, w], out [buffer, 8h, 8w], ix [n]")
+    nbuf_in, h, w = (int(v) for v in disps.shape)
+    if tuple(out.shape[1:]) != (8 * h, 8 * w):
+        raise RuntimeError(f"upsample_disps: out must be [buffer, {8 * h}, {8 * w}], got {tuple(out.shape)}")
+    n = int(ix.shape[0])
+    mask = _upsample_args("upsample_disps", mask, n, h, w, ((disps, "disps"), (out, "out")), ix)
+    _lib.check(lib.droid_cvx_upsample(disps.data_ptr(), ix.data_ptr(), mask.data_ptr(), out.data_ptr(), n, nbuf_in,
+                                      int(out.shape[0]), h, w, _DT[mask.dtype], _stream()), "upsample_disps")
+    return out
+
+
+def cvx_upsample(data, mask):
+    """Drop-in for `droid_net.cvx_upsample` (droid_net.py:21-35) in the one form the reference calls it with:
+    data [batch, ht, wd, 1] float32, mask anything that views to [batch, 576, ht, wd] (float16 or float32).  Returns a
+    new [batch, 8 ht, 8 wd, 1] float32 tensor (droid_cvx_upsample with ix = NULL).  Inference only: no autograd."""
+    lib = _lib.load()
+    if data.dim() != 4 or data.shape[-1] != 1:
+        raise RuntimeError(f"cvx_upsample: data must be [batch, ht, wd, 1] -- only dim = 1 (a disparity map) is "
+                           f"supported, got {tuple(data.shape)}")
+    if torch.is_grad_enabled() and (data.requires_grad or mask.requires_grad):
+        raise RuntimeError("cvx_upsample: no autograd -- training keeps the stock droid_net.cvx_upsample")
+    batch, ht, wd = (int(v) for v in data.shape[:3])
+    if not mask.is_contiguous():
+        raise RuntimeError("cvx_upsample: mask must be contiguous")
+    if mask.numel() != batch * 576 * ht * wd:
+        raise RuntimeError(f"cvx_upsample: mask must view to [{batch}, 576, {ht}, {wd}], got {tuple(mask.shape)}")
+    mask = _upsample_args("cvx_upsample", mask.view(batch, 576, ht, wd), batch, ht, wd, ((data, "data"),))
+    out = torch.empty((batch, 8 * ht, 8 * wd, 1), dtype=torch.float32, device=data.device)
+    _lib.check(lib.droid_cvx_upsample(data.data_ptr(), None, mask.data_ptr(), out.data_ptr(), batch, batch, batch, ht, wd,
+                                      _DT[mask.dtype], _stream()), "cvx_upsample")
+    return out
 
 
 def _corr_dtype(t, name):

@@ -26,6 +26,7 @@ SYMBOLS = [
     "droid_ba_attach_status_mirror", "droid_ba_attach_launch_hints", "droid_chol_solve", "droid_chol_scratch_doubles", "droid_reproject_motion",
     "droid_frame_distance", "droid_frame_distance_matrix", "droid_projmap", "droid_iproj", "droid_depth_filter",
     "droid_proximity_workspace_bytes", "droid_proximity_edges",
+    "droid_cvx_upsample",
 ]
 
 DROID_F16, DROID_F32, DROID_F64 = 0, 1, 2
@@ -99,6 +100,7 @@ def load() -> ctypes.CDLL:
     lib.droid_proximity_workspace_bytes.restype = sz
     lib.droid_proximity_edges.argtypes = ([vp] + [c_int] * 7 + [c_float, c_int, c_int, vp, vp, c_int, vp, vp, c_int,
                                                                 vp, c_int, vp, vp, sz, vp])
+    lib.droid_cvx_upsample.argtypes = [vp] * 4 + [c_int] * 6 + [vp]
     for s in SYMBOLS[2:]:
         if s not in ("droid_ba_workspace_bytes", "droid_ba_system", "droid_ba_packed_system", "droid_chol_scratch_doubles",
                      "droid_proximity_workspace_bytes"):

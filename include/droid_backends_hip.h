@@ -333,6 +333,35 @@ int droid_depth_filter(const float *poses, const float *disps, const float *intr
                        const int64_t *ix, const float *thresh, int num, int nbuf, int H, int W,
                        float *counter, void *stream);
 
+/* ------------------------------------------------------------------ convex upsampling */
+
+/* `DepthVideo.upsample` (droid_slam/depth_video.py:134-138) with `cvx_upsample` (droid_net.py:21-35) behind it, in one
+ * launch: the gather `disps[ix]`, softmax over the 9 taps, the 3x3 unfold, the weighted sum, the pixel shuffle and the
+ * scatter `disps_up[ix] = ...`.  Not one of the reference's nine operators.
+ * data [nbuf_in, H, W] f32, the disparity buffer as DepthVideo holds it (only read) ; out [nbuf_out, 8H, 8W] f32 ;
+ * mask [n, 576, H, W] of mask_dtype (DROID_F16 or DROID_F32), contiguous, channel c = (k*8 + a)*8 + b with k = ky*3 + kx
+ * the tap of the 3x3 neighbourhood and (a, b) the sub-pixel row and column (the reference's
+ * `view(batch, 1, 9, 8, 8, ht, wd)`) ; ix [n] int64 on the DEVICE, or NULL for the identity.
+ * Entry e uses frame f = ix[e] (e when ix is NULL): it reads data[f] and mask[e] and writes out[f] completely,
+ *   out[f, 8y+a, 8x+b] = sum_k w_k * P(y + ky - 1, x + kx - 1),   w = softmax_k(mask[e, (k*8+a)*8+b, y, x]),
+ * P = data[f] with zero outside the image (F.unfold(., [3,3], padding=1)).  No other frame of out is touched.
+ * Arithmetic, all in fp32: half logits widened exactly, the maximum subtracted first (logits of +-65504 cannot
+ * overflow), expf, the sum in ascending k, one division per weight, the products accumulated in ascending k (the first
+ * a multiplication, the other eight fused multiply-adds); the weights are never rounded to half, unlike
+ * `torch.softmax` of a half mask.  Every output pixel is within 32 * 2^-24 * (max |P| over its neighbourhood) of the
+ * fp64 evaluation.  No atomics: the same bits on every run, and the bits of a frame do not depend on n or
+ * on the entry's position in the batch.
+ * The host never reads ix, so it is checked on the device: an entry whose frame is outside [0, min(nbuf_in, nbuf_out))
+ * is skipped -- nothing is read or written for it (the convention of droid_corr_volume_pyramid_slots).  Two entries that
+ * name one frame violate the contract: which entry's bits land there is unspecified (nothing outside that frame is
+ * written).
+ * DROID_E_ARG with a message: mask_dtype not F16 / F32 ; H < 1 or W < 1 ; n < 0 ; nbuf_in < 1 or nbuf_out < 1 ; a null
+ * data, mask or out with n > 0 ; 8H * 8W * nbuf_out (or 576 * H * W * n) beyond 2^62 elements, or H * W beyond
+ * 2^31 - 65 (the kernel's index types).  All checks are host-side and precede any HIP call; n == 0 launches nothing and
+ * returns 0.  Any n an int holds (launched in slabs of 65535); any H, W >= 1: no alignment requirement, no fallback. */
+int droid_cvx_upsample(const float *data, const int64_t *ix, const void *mask, float *out, int n, int nbuf_in,
+                       int nbuf_out, int H, int W, int mask_dtype, void *stream);
+
 /* ------------------------------------------------------------------ factor-graph edge selection */
 
 /* The edge list `FactorGraph.add_proximity_factors` (droid_slam/factor_graph.py:315-379) hands to `add_factors`,
