@@ -10,6 +10,8 @@
 // each product is rounded to the element type, and the four contributions of one output are
 // added in the order taps (a,c), (a,c+1), (a+1,c), (a+1,c+1) with a rounding after every add
 // (correlation_kernels.cu:46-66; a = x offset, c = y offset).
+#include <cfloat>
+
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -72,7 +74,14 @@ __device__ __forceinline__ Bilin bilin_setup(float x0, float y0, int r) {
   const float lim = 1.0e6f;
   b.x1 = (int)fminf(fmaxf(fx, -lim), lim) - r;
   b.y1 = (int)fminf(fmaxf(fy, -lim), lim) - r;
-  if (!(x0 == x0) || !(y0 == y0)) { b.x1 = -2000000; b.y1 = -2000000; }
+  // A NaN or infinite coordinate has an empty window and returns zeros (oracle/corr.py; what the reference gives for
+  // +-inf).  The window alone is not enough: x0 - floor(x0) is NaN for all three, every weight would be NaN and every
+  // output 0 * NaN.  With dx = dy = 0 the weights are (1, 0, 0, 0) against taps that are all zero: +0 in every
+  // element type and in every kernel that starts here.  fabsf(x) <= FLT_MAX is false for NaN and for +-inf.
+  if (!(fabsf(x0) <= FLT_MAX) || !(fabsf(y0) <= FLT_MAX)) {
+    b.x1 = -2000000; b.y1 = -2000000;
+    b.dx = 0.f; b.dy = 0.f;
+  }
   return b;
 }
 

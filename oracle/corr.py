@@ -135,6 +135,11 @@ def altcorr_forward(fmap1, fmap2, coords, radius, acc_dtype=None, chunked=True):
         for n in range(N):
             x2 = coords[:, n, :, :, 0]
             y2 = coords[:, n, :, :, 1]
+            # a NaN or infinite coordinate has an empty window and gives zeros, like corr_index_forward above (the
+            # reference's bounds test rejects every tap of a +-inf query; NaN has no defined integer tap at all)
+            fin = np.isfinite(x2) & np.isfinite(y2)
+            x2 = np.where(fin, x2, np.float32(-2e6))
+            y2 = np.where(fin, y2, np.float32(-2e6))
             fx = np.floor(x2)
             fy = np.floor(y2)
             dx = (x2 - fx).astype(np.float32)  # ak:78-79
@@ -194,6 +199,8 @@ def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
     one = np.float32(1.0)
     for n in range(N):
         x2, y2 = coords[:, n, :, :, 0], coords[:, n, :, :, 1]
+        fin = np.isfinite(x2) & np.isfinite(y2)   # NaN / +-inf: empty window, no gradient (see altcorr_forward)
+        x2, y2 = np.where(fin, x2, np.float32(-2e6)), np.where(fin, y2, np.float32(-2e6))
         fx, fy = np.floor(x2), np.floor(y2)
         dx = (x2 - fx).astype(np.float32)
         dy = (y2 - fy).astype(np.float32)

@@ -1,0 +1,316 @@
+"""CPU proof that tests/corr_cases.py reaches every path the dispatch of csrc/corr.hip can take and every per-tile
+branch of its tiled kernels, that the constants of the restatement are those of the source, pins of oracle/corr.py in
+the regimes the table adds, and that the componentwise bars are ones a correct fp32 evaluation meets."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import corr_cases as cc
+
+SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "droid-slam_reserch_amd", "csrc", "corr.hip")
+
+
+def _src():
+    with open(SRC) as f:
+        return f.read()
+
+
+def test_constants_match_the_source():
+    s = _src()
+    def const(name):
+        m = re.search(r"constexpr int (?:[A-Z_]+ = \d+, )*" + name + r" = (\d+)", s)
+        assert m, name
+        return int(m.group(1))
+    for name in ("CS_MAXPLANE", "ALT_TQ", "ALT_MAXPOS", "ALT_CH", "AM_TX", "AM_TY", "AM_MAXBLK", "AM_MAXPOS", "ABT", "AB_CH",
+                 "AB_MAXPOS", "G1MAX"):
+        assert const(name) == getattr(cc, name), name
+    assert re.search(r"XBLK = \(R <= 3\) \? (\d+) : AM_MAXBLK;", s).group(1) == str(cc.AM_XBLK[3])
+    assert cc.AM_XBLK[4] == cc.AM_MAXBLK
+    m = re.search(r"MAXBLK = \(R <= 3\) \? (\d+) : (\d+);", s)
+    assert (int(m.group(1)), int(m.group(2))) == (cc.AW_MAXBLK[3], cc.AW_MAXBLK[4])
+    chs = re.findall(r"static constexpr int CH = (\d+);", s)
+    sts = re.findall(r"static constexpr int MAXSTAGE = (\d+);", s)
+    assert [int(c) for c in chs] == [cc.AM_CH["f32"], cc.AM_CH["f16"]]
+    assert [int(c) for c in sts] == [cc.AM_MAXSTAGE["f32"], cc.AM_MAXSTAGE["f16"]]
+    # the conditions the restatement copies, as written in the launchers
+    for text in ("PB > CS_MAXPLANE || (PB & 15) != 0 || (reinterpret_cast<uintptr_t>(v) & 15) != 0",
+                 "W2 * (int)sizeof(T) > 64 || (HW & 63) != 0", "R != 3 || sizeof(T) > 4",
+                 "(C % AB_CH) == 0 && (r == 3 || r == 4)", "g1_regs = C <= 16 * G1MAX",
+                 "fits = fits && (sw_ * sh_ <= 16 * AM_MAXBLK)", "two_rounds = two_rounds || (sw_ * sh_ > 16 * AM_XBLK)",
+                 "fits = fits && npos <= AM_MAXPOS", "nposw > 16 * MAXBLK", "npos > AB_MAXPOS", "npos > ALT_MAXPOS",
+                 "const float lim = 1.0e6f;", "b.x1 = -2000000; b.y1 = -2000000;"):
+        assert text in s, text
+
+
+def test_volume_table_reaches_every_reachable_path(capsys):
+    reach = cc.reachable_volume_tuples()
+    by = {}
+    for c in cc.VOLUME_CASES:
+        for t in c.tuples():
+            by.setdefault(t, c.id)
+    with capsys.disabled():
+        print("\npath     dtype r slotted entry    first case")
+        for t in sorted(reach, key=str):
+            print(f"{t[0]:8s} {t[1]:5s} {t[2]} {str(t[3]):7s} {t[4]:8s} {by.get(t, 'MISSING')}")
+    assert set(by) == reach, sorted(reach - set(by), key=str)
+    # what the issue names one by one
+    for t in (("row", "f16", 4, False, "index"), ("row", "f32", 4, False, "index"), ("small", "f16", 4, False, "index"),
+              ("small", "f32", 4, False, "index"), ("small", "f64", 4, False, "index"), ("small", "f64", 3, False, "index"),
+              ("generic", "f16", 5, False, "index"), ("generic", "f32", 2, False, "index"), ("coop", "f16", 3, True, "slots")):
+        assert t in by, t
+    # the storage-offset views: `small` refuses the base, and each of coop / row / generic sees one
+    off = {(p, c.dtype) for c in cc.VOLUME_CASES if c.offset for p in c.paths()}
+    assert {("coop", "f16"), ("coop", "f32"), ("row", "f16"), ("row", "f32"), ("row", "f64"), ("generic", "f16")} <= off
+    assert not any(p == "small" for p, _ in off)
+    # a partial wave and a second, partial workgroup in `small`; a second workgroup in the row kernel
+    small_hw = {c.qmap[0] * c.qmap[1] for c in cc.VOLUME_CASES if "small" in c.paths()}
+    assert {63, 72} <= small_hw
+    assert any(c.qmap == (16, 20) and "row" in c.paths() for c in cc.VOLUME_CASES)
+    ids = [c.id for c in cc.VOLUME_CASES]
+    assert len(set(ids)) == len(ids)
+
+
+def test_volume_cases_hold_every_coordinate_kind_and_stay_finite(oracle):
+    """Every case carries every coordinate kind; on a wide-exponent half volume the taps are subnormal and the partial sums of
+    one output differ by more than 13 binades, with all sums finite (array_equal must not compare NaN)."""
+    for c in cc.VOLUME_CASES[::9]:
+        vols, coords, kind = c.build()
+        assert set(np.unique(kind)) == set(range(len(cc.KINDS))), c.id
+        nf = kind == cc.KINDS.index("nonfinite")
+        assert not np.isfinite(coords).all(1)[nf].any() and np.isfinite(coords).all(1)[~nf].all()
+        x1, y1 = cc.bilin_origin(coords[:, 0], coords[:, 1], c.r)
+        h, w = c.levels[0]
+        nt = 2 * c.r + 2
+        emp = kind == cc.KINDS.index("empty")
+        assert ((x1[emp] + nt <= 0) | (x1[emp] >= w) | (y1[emp] + nt <= 0) | (y1[emp] >= h)).all(), c.id
+        bd = kind == cc.KINDS.index("border")
+        assert ((x1[bd] < 0) | (x1[bd] + nt > w) | (y1[bd] < 0) | (y1[bd] + nt > h)).all(), c.id
+    wide = next(c for c in cc.VOLUME_CASES if c.values == "wide" and c.dtype == "f16" and c.r == 4 and c.levels[0] == (24, 32))
+    vols, coords, _ = wide.build()
+    v = vols[0]
+    assert (np.abs(v) < 2.0 ** -14).mean() > 0.2 and (np.abs(v) > 256).mean() > 0.05     # subnormal taps and large ones
+    out = oracle.corr_index_forward(v, coords, wide.r)
+    assert np.isfinite(out).all()
+
+
+@pytest.mark.parametrize("r", [1, 2, 4, 5])
+def test_corr_index_is_bilinear_sampling_at_other_radii(oracle, r):
+    """The grid_sample identity of test_oracle_corr.py at the radii the table adds (fp64, zero padding)."""
+    rng = np.random.default_rng(r)
+    B, H, W, H2, W2 = 2, 5, 6, 9, 11
+    vol = rng.normal(0, 1, (B, H, W, H2, W2))
+    coords = np.stack([rng.uniform(-r - 2, W2 + r + 1, (B, H, W)), rng.uniform(-r - 2, H2 + r + 1, (B, H, W))], 1).astype(np.float32)
+    out = oracle.corr_index_forward(vol, coords, r)
+    planes = torch.from_numpy(vol.reshape(B * H * W, 1, H2, W2))
+    x0 = torch.from_numpy(coords[:, 0].reshape(-1).astype(np.float64))
+    y0 = torch.from_numpy(coords[:, 1].reshape(-1).astype(np.float64))
+    for a in range(2 * r + 1):
+        for c in range(2 * r + 1):
+            grid = torch.stack([(x0 - r + a) / (W2 - 1) * 2 - 1, (y0 - r + c) / (H2 - 1) * 2 - 1], -1).view(-1, 1, 1, 2)
+            s = F.grid_sample(planes, grid, mode="bilinear", padding_mode="zeros", align_corners=True)
+            assert np.abs(out[:, a, c] - s.view(B, H, W).numpy()).max() < 1e-6
+
+
+@pytest.mark.parametrize("r", [1, 3, 4])
+def test_corr_index_backward_is_the_adjoint_of_the_forward(oracle, r):
+    """<corr(V), G> = <V, backward(G)> in fp64, border, empty and non-finite queries included, and the gradient is zero
+    where no window reaches."""
+    from oracle import corr as oc
+    rng = np.random.default_rng(10 + r)
+    B, H1, W1, H2, W2, rd = 2, 5, 7, 6, 9, 2 * r + 1
+    x, y, _ = cc.edge_coords(rng, B * H1 * W1, r, H2, W2)
+    coords = np.stack([x.reshape(B, H1, W1), y.reshape(B, H1, W1)], 1)
+    G = rng.normal(size=(B, rd, rd, H1, W1))
+    with np.errstate(invalid="ignore"):
+        g = oc.corr_index_backward((B, H1, W1, H2, W2), coords, G, r)
+        assert np.isfinite(g).all()
+        for seed in (1, 2):
+            V = np.random.default_rng(seed).normal(size=(B, H1, W1, H2, W2))
+            lhs, rhs = np.sum(oc.corr_index_forward(V, coords, r) * G), np.sum(V * g)
+            assert abs(lhs - rhs) < 1e-10 * max(1.0, abs(lhs)), (lhs, rhs)
+    x1, y1 = cc.bilin_origin(coords[:, 0], coords[:, 1], r)
+    yy, xx = np.arange(H2)[:, None], np.arange(W2)[None, :]
+    reach = ((xx >= x1[..., None, None]) & (xx < x1[..., None, None] + rd + 1) &
+             (yy >= y1[..., None, None]) & (yy < y1[..., None, None] + rd + 1))
+    assert not g[~reach].any()
+
+
+def test_half_rounding_points_on_a_wide_exponent_volume(oracle):
+    """On magnitudes 2^U(-24, 12) the half restatement still rounds every product and every partial sum to half:
+    each output is reproduced by an explicit half-by-half evaluation of its four taps, and differs from fp64."""
+    rng = np.random.default_rng(5)
+    B, H, W, H2, W2, r = 1, 4, 5, 8, 8, 3
+    vol = (np.exp2(rng.uniform(-24, 12, (B, H, W, H2, W2))) * rng.choice([-1.0, 1.0], (B, H, W, H2, W2))).astype(np.float16)
+    coords = np.stack([rng.uniform(3, 4, (B, H, W)), rng.uniform(3, 4, (B, H, W))], 1).astype(np.float32)   # windows inside
+    out = oracle.corr_index_forward(vol, coords, r)
+    assert out.dtype == np.float16 and np.isfinite(out).all()
+    dx = coords[:, 0] - np.floor(coords[:, 0])
+    dy = coords[:, 1] - np.floor(coords[:, 1])
+    one = np.float32(1)
+    h = np.float16
+    w00, w01, w10, w11 = h((one - dx) * (one - dy)), h((one - dx) * dy), h(dx * (one - dy)), h(dx * dy)
+    x1 = np.floor(coords[:, 0]).astype(int) - r
+    y1 = np.floor(coords[:, 1]).astype(int) - r
+    bb, yy, xx = np.meshgrid(np.arange(B), np.arange(H), np.arange(W), indexing="ij")
+    tap = lambda i, j: vol[bb, yy, xx, y1 + j, x1 + i]
+    for a in range(7):
+        for c in range(7):
+            acc = h(tap(a, c) * w00)                       # numpy half ops: fp32 compute, one rounding to half
+            acc = h(acc + h(tap(a, c + 1) * w01))
+            acc = h(acc + h(tap(a + 1, c) * w10))
+            acc = h(acc + h(tap(a + 1, c + 1) * w11))
+            assert np.array_equal(out[:, a, c], acc)
+    ref = oracle.corr_index_forward(vol.astype(np.float64), coords, r)
+    assert np.abs(out.astype(np.float64) - ref).max() > 0
+
+
+def test_non_finite_coordinates_give_zeros_in_every_oracle(oracle):
+    """The contract of the non-finite queries: an empty window, zeros forward, no gradient backward."""
+    from oracle import corr as oc
+    rng = np.random.default_rng(6)
+    B, H, W, C, r = 1, 2, 3, 8, 3
+    xy = np.array(cc.NONFINITE, np.float32).reshape(B, H, W, 2)
+    with np.errstate(invalid="ignore"):
+        vol = rng.normal(size=(B, H, W, 5, 6)).astype(np.float32)
+        out = oracle.corr_index_forward(vol, np.ascontiguousarray(xy.transpose(0, 3, 1, 2)), r)
+        assert out.shape == (B, 7, 7, H, W) and not out.any()
+        f1, f2 = rng.normal(size=(B, H, W, C)), rng.normal(size=(B, 5, 6, C))
+        for acc in (np.float64, np.float32):
+            alt = oc.altcorr_forward(f1, f2, xy[:, None], r, acc_dtype=acc)
+            assert alt.shape == (B, 1, 49, H, W) and not alt.any()
+        g1, g2 = oc.altcorr_backward(f1, f2, xy[:, None], rng.normal(size=(B, 1, 49, H, W)), r)
+        assert not g1.any() and not g2.any()
+        gv = oc.corr_index_backward(vol.shape, np.ascontiguousarray(xy.transpose(0, 3, 1, 2)), rng.normal(size=out.shape), r)
+        assert not gv.any()
+
+
+def test_alt_tables_reach_every_path_and_every_tile_class(capsys):
+    fwd = {}
+    for c in cc.ALT_FORWARD_CASES:
+        fwd.setdefault((c.forward_path(), c.dtype, c.r), c.id)
+    for want in (("generic", "f64", 2), ("generic", "f64", 3), ("generic", "f16", 3), ("generic", "f32", 5),
+                 ("mfma_f32", "f32", 3), ("mfma_f32", "f32", 4), ("wave_f16", "f16", 3), ("wave_f16", "f16", 4),
+                 ("tiled", "f32", 3), ("tiled", "f32", 4)):
+        assert want in fwd, want
+    assert {(c.C, c.r) for c in cc.ALT_FORWARD_CASES if c.dtype == "f64"} == {(24, 2), (40, 3), (40, 2), (24, 3)}
+    # the half matrix-core instantiation needs a query map of 2^30 elements: nothing the suite can hold reaches it
+    assert cc.alt_forward_path("f16", 3, 128, 1 << 12, 1 << 11, 8, 8) == "mfma_f16"
+    assert cc.alt_forward_path("f16", 3, 128, 1 << 11, 1 << 11, 8, 8) == "wave_f16"
+    bwd = {(c.backward_path(), c.r) for c in cc.ALT_BACKWARD_CASES}
+    assert bwd >= {("tiled", 3), ("tiled", 4), ("per_tap_regs", 3), ("per_tap_regs", 2), ("per_tap_atomics", 3)}
+    assert cc.alt_backward_path(3, 272) == "tiled" and cc.alt_backward_path(3, 264) == "per_tap_atomics"
+    assert cc.alt_backward_path(3, 40) == "per_tap_regs" and cc.alt_backward_path(2, 32) == "per_tap_regs"
+
+    # every alt-corr case, forward and backward, holds NaN in x only, NaN in y only, +inf and -inf in every (b, n)
+    for c in cc.ALT_BACKWARD_CASES + cc.ALT_FORWARD_CASES:
+        _, _, coords = c.build()
+        x, y = coords[..., 0].reshape(c.B * c.N, -1), coords[..., 1].reshape(c.B * c.N, -1)
+        for name, m in (("NaN in x only", np.isnan(x) & np.isfinite(y)), ("NaN in y only", np.isfinite(x) & np.isnan(y)),
+                        ("+inf", np.isposinf(x) | np.isposinf(y)), ("-inf", np.isneginf(x) | np.isneginf(y))):
+            assert m.any(1).all(), (c.id, name)
+
+    seen, lines, nf_seen = {}, [], set()
+    for c in cc.ALT_BACKWARD_CASES:
+        if c.backward_path() != "tiled":
+            continue
+        _, _, coords = c.build()
+        kl = cc.backward_tile_classes(coords, c.r, *c.fmap2)
+        nf_seen |= {("backward", str(k)) for k in np.unique(kl[cc.nonfinite_tiles(coords, cc.ABT, cc.ABT)])}
+        sh = cc.class_shares(cc.backward_tile_classes(coords, c.r, *c.fmap2))
+        lines.append(f"backward tiled  {c.id:32s} " + " ".join(f"{k}={v:.2f}" for k, v in sh.items()))
+        for k in sh:
+            seen.setdefault(("backward", k), c.id)
+        for k in cc.ALT_BACKWARD_DOMINANT.get(c.id, ()):
+            assert sh.get(k, 0) >= 0.25, (c.id, sh)
+    kernel = {"mfma_f32": "mfma", "wave_f16": "wave", "tiled": "tiled"}
+    for c in cc.ALT_FORWARD_CASES:
+        _, _, coords = c.build()
+        cls = cc.forward_tile_classes(c, coords)
+        if cls is None:
+            continue
+        sh = cc.class_shares(cls)
+        nf_seen |= {(kernel[c.forward_path()], str(k), c.r)
+                    for k in np.unique(cls[cc.nonfinite_tiles(coords, *cc.FORWARD_TILE[c.forward_path()])])}
+        lines.append(f"forward {kernel[c.forward_path()]:6s}  {c.id:32s} " + " ".join(f"{k}={v:.2f}" for k, v in sh.items()))
+        for k in sh:
+            seen.setdefault((kernel[c.forward_path()], k, c.r), c.id)
+        if c.id in cc.ALT_FORWARD_DOMINANT:
+            kn, k = cc.ALT_FORWARD_DOMINANT[c.id]
+            assert kn == kernel[c.forward_path()] and sh.get(k, 0) >= 0.25, (c.id, sh)
+    # what the jitters of the older tests reach (their docstrings name branches; this is the record)
+    # corr_cases.legacy_*_coords repeat the generator calls of those tests: if their text moves, this record is stale
+    here = os.path.dirname(os.path.abspath(__file__))
+    for fn, texts in (("test_gpu_corr.py", ('[(2.6, 128, 16, 32), (10.0, 64, 12, 16), (1.0, 48, 9, 19), (1.5, 256, 8, 16)]',
+                                            "rng = np.random.default_rng(int(jitter * 10) + C)",
+                                            "cx = xx[None] + rng.uniform(-jitter, jitter, (2, H, W))")),
+                      ("test_gpu_baseline_shapes.py", ("[(32, 3, 0.5), (96, 3, 6.0), (96, 4, 1.5), (64, 4, 40.0)]",
+                                                       "rng = np.random.default_rng(7 * C + r)", "F, H, W = 3, 10, 13"))):
+        with open(os.path.join(here, fn)) as f:
+            text = f.read()
+        for t in texts:
+            assert t in text, (fn, t)
+    legacy = {}
+    for a in ((2.6, 128, 16, 32), (10.0, 64, 12, 16)):
+        legacy[("mfma", a[0])] = cc.class_shares(cc.mfma_tile_classes(cc.legacy_mfma_coords(*a), 3, a[2], a[3]))
+    for a in ((96, 3, 6.0), (64, 4, 40.0)):
+        legacy[("wave", a[2])] = cc.class_shares(cc.wave_tile_classes(cc.legacy_wave_coords(*a), a[1], 10, 13))
+    for k, sh in legacy.items():
+        lines.append(f"older test {k[0]} jitter {k[1]:<5g}" + " " * 19 + " ".join(f"{n}={v:.2f}" for n, v in sh.items()))
+    with capsys.disabled():
+        print("\n" + "\n".join(lines))
+    assert legacy[("mfma", 2.6)].get("two_rounds", 0) >= 0.25
+    # 12x16 and 10x13 maps hold 192 and 130 positions: no box on them can exceed 240 (320), so jitter 10 and 40 never
+    # left the box path.  The per-query branches are reached by the cases of this table only.
+    assert set(legacy[("mfma", 10.0)]) == {"one_round"} and set(legacy[("wave", 40.0)]) == {"box_gemm"}
+    for want in (("backward", "empty"), ("backward", "hit_lists"), ("backward", "incoherent"),
+                 ("mfma", "one_round", 3), ("mfma", "two_rounds", 3), ("mfma", "per_query", 3), ("mfma", "one_round", 4),
+                 ("mfma", "per_query", 4), ("wave", "box_gemm", 3), ("wave", "per_query", 3), ("wave", "box_gemm", 4),
+                 ("wave", "per_query", 4), ("tiled", "staged", 3), ("tiled", "per_query", 4)):
+        assert want in seen, want
+        assert want in nf_seen, ("no non-finite query in a tile of this class", want)
+    # both classes in ONE launch of the mixed case, and an empty tile next to them
+    _, _, coords = next(c for c in cc.ALT_BACKWARD_CASES if c.id == "mixed-r3-C16").build()
+    assert set(np.unique(cc.backward_tile_classes(coords, 3, 24, 24)[0, 0])) == {"empty", "hit_lists", "incoherent"}
+
+
+@pytest.mark.parametrize("case", [c for c in cc.ALT_FORWARD_CASES if c.dtype != "f64"], ids=lambda c: c.id)
+def test_fp32_restatement_meets_the_forward_bound(oracle, case):
+    """The componentwise bar of the GPU test is one a correct implementation meets: the fp32 restatement of the
+    reference's evaluation (sequential, 32-channel chunks) stays inside it on every element of every case."""
+    from oracle import corr as oc
+    f1, f2, coords = case.build()
+    a, b = f1.astype(np.float64), f2.astype(np.float64)
+    ref = oc.altcorr_forward(a, b, coords, case.r, acc_dtype=np.float64)
+    abs_sum = oc.altcorr_forward(np.abs(a), np.abs(b), coords, case.r, acc_dtype=np.float64)
+    got = oc.altcorr_forward(f1.astype(np.float32), f2.astype(np.float32), coords, case.r, acc_dtype=np.float32)
+    bound = cc.forward_bound(case, abs_sum, ref)
+    err = np.abs(got.astype(np.float64) - ref)
+    assert (err <= bound).all(), float((err / np.maximum(bound, 1e-300)).max())
+    assert not got[abs_sum == 0].any()
+
+
+def test_half_restatement_meets_the_generic_f16_bound(oracle):
+    """The 2^-11 part of the bar for the generic kernel on f16: a restatement with that kernel's rounding points (tap sums
+    formed in fp32 and rounded to half, then weights, products and partial sums rounded to half, which is the volume
+    lookup of the half volume of tap sums) stays inside corr_cases.forward_bound, and needs more than the fp32 bar."""
+    from oracle import corr as oc
+    case = next(c for c in cc.ALT_FORWARD_CASES if c.dtype == "f16" and c.forward_path() == "generic")
+    f1, f2, coords = case.build()
+    a, b = f1.astype(np.float64), f2.astype(np.float64)
+    ref = oc.altcorr_forward(a, b, coords, case.r, acc_dtype=np.float64)
+    abs_sum = oc.altcorr_forward(np.abs(a), np.abs(b), coords, case.r, acc_dtype=np.float64)
+    vol = np.einsum("bhwc,bijc->bhwij", f1.astype(np.float32), f2.astype(np.float32)).astype(np.float16)
+    rd2 = (2 * case.r + 1) ** 2
+    with np.errstate(invalid="ignore"):
+        got = np.stack([oracle.corr_index_forward(vol, np.ascontiguousarray(coords[:, n].transpose(0, 3, 1, 2)), case.r)
+                        .reshape(case.B, rd2, *case.qmap) for n in range(case.N)], 1)
+    assert got.dtype == np.float16 and got.shape == ref.shape
+    err = np.abs(got.astype(np.float64) - ref)
+    bound = cc.forward_bound(case, abs_sum, ref)
+    assert (err <= bound).all(), float((err / np.maximum(bound, 1e-300)).max())
+    assert (err > (case.C + cc.COMBINE_OPS) * cc.U32 * abs_sum + cc.U16 * np.abs(ref) + 2.0 ** -25).any()
+    assert not got[abs_sum == 0].any()

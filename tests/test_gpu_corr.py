@@ -103,8 +103,9 @@ def _alt_inputs(B, H, W, lvl, C, seed):
 def test_altcorr_backward_matches_oracle(backends, oracle, lvl, C, N, r):
     """fmap gradients of altcorr (altcorr_kernel.cu:152-286) against the fp64 restatement (itself checked to be
     the adjoint of the forward, tests/test_oracle_corr.py): fp32 atomics, 2e-5 of the gradient scale; the
-    coordinate gradient is identically zero like the reference's.  C = 272 takes the path without the register
-    accumulation of the query's own gradient, C = 40 a channel count that is not a multiple of 16."""
+    coordinate gradient is identically zero like the reference's.  C = 272 is a multiple of 16 and runs the tiled
+    kernel with 17 channel passes; C = 40, no multiple of 16, runs the per-tap kernel with its register sums (the
+    per-tap kernel's atomic branch, C > 256 and no multiple of 16, is in tests/test_gpu_corr_paths.py)."""
     torch = _torch()
     from oracle import corr as oc
     f1, f2, coords = _alt_inputs(2, 12, 16, lvl, C, seed=10 + lvl)
