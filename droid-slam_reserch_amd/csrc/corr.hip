@@ -11,6 +11,7 @@
 // added in the order taps (a,c), (a,c+1), (a+1,c), (a+1,c+1) with a rounding after every add
 // (correlation_kernels.cu:46-66; a = x offset, c = y offset).
 #include <cfloat>
+#include <type_traits>
 
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -83,6 +84,31 @@ __device__ __forceinline__ Bilin bilin_setup(float x0, float y0, int r) {
     b.dx = 0.f; b.dy = 0.f;
   }
   return b;
+}
+
+// The four bilinear weights of a query, each formed in fp32 and rounded to the element type (ck:55-65): wAC belongs to the
+// tap at x offset +A, y offset +C.  Every lookup kernel and the gradient take them from here.
+template <typename T>
+struct Weights {
+  typename Elem<T>::work w00, w01, w10, w11;
+};
+template <typename T>
+__device__ __forceinline__ Weights<T> bilin_weights(const Bilin& bl) {
+  typedef typename Elem<T>::work work;
+  const float one = 1.0f;
+  Weights<T> w;
+  w.w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )
+  w.w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
+  w.w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
+  w.w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
+  return w;
+}
+
+// r == 3 / r == 4 -> template argument: calls f(std::integral_constant<int, r>{}).  Every launcher below checks the
+// radius before it comes here.
+template <typename F>
+static void with_radius(int r, F&& f) {
+  if (r == 3) f(std::integral_constant<int, 3>{}); else f(std::integral_constant<int, 4>{});
 }
 
 // ---- the bilinear combine of one query: (2r+1)^2 outputs from (2r+2)^2 taps ---------------------------------
@@ -200,6 +226,7 @@ struct RowLoad<__half, NT> {
 
 template <int NT>
 struct RowLoad<float, NT> {
+  static constexpr int NW = NT;
   static __device__ __forceinline__ void load(const float* p, float* tap) {
     const u32a4* q = reinterpret_cast<const u32a4*>(p);
 #pragma unroll
@@ -217,9 +244,52 @@ struct RowLoad<double, NT> {
   static __device__ __forceinline__ size_t span_bytes() { return NT * 8; }
 };
 
+// May the dword-aligned wide load of the NT taps at rp (RowLoad) run?  Only if it stays inside the tensor [vbeg, vend).
+template <typename T, int NT>
+__device__ __forceinline__ bool row_load_ok(const T* rp, uintptr_t vbeg, uintptr_t vend) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(rp) & ~uintptr_t(3);
+  return a0 >= vbeg && a0 + RowLoad<T, NT>::span_bytes() <= vend;
+}
+
+// What the three fast lookup kernels below share: the query of one lane (slot, window origin, weights) and the combine.
+// Each kernel gathers the window its own way in between (corr_index_forward_small never reads xany: its taps are guarded
+// one by one).
 // out_bstride: elements between the outputs of consecutive batch entries ((2r+1)^2 H1W1 for the reference's operator;
 // levels (2r+1)^2 H1W1 when the levels of a pyramid are written side by side, corr_pyramid_forward); cscale: the
 // coordinates are multiplied by it first (1, or 2^-level: exact).
+template <typename T, int R, bool SLOTTED>
+struct Lookup {
+  typedef typename Elem<T>::work work;
+  static constexpr int RD = 2 * R + 1, NT = RD + 1;
+  size_t slot;  // of batch entry b: b itself unless SLOTTED
+  bool live;    // false: a slot outside the buffer (SLOTTED only), the query returns zeros
+  Bilin bl;
+  bool xany;    // any tap of the window inside the plane's columns at all?
+
+  // The slot comes first and alone: corr_index_forward_small stages the planes of it before it needs a coordinate.
+  __device__ __forceinline__ Lookup(const int64_t* __restrict__ slots, long long cap, int b) : slot((size_t)b), live(true) {
+    if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
+  }
+  // valid = false: a lane without a query (pix is then any pixel that exists)
+  __device__ __forceinline__ void locate(const float* __restrict__ coords, int b, int pix, int H1W1, int W2, float cscale,
+                                         bool valid = true) {
+    const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale;
+    const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale;
+    bl = bilin_setup(x0, y0, R);
+    xany = valid && live && (bl.x1 + NT > 0) && (bl.x1 < W2);
+  }
+  // weights (all zero for a dead slot) and the combine into the (2r+1)^2 output planes of (b, pix)
+  __device__ __forceinline__ void combine(const work (&tap)[NT][NT], T* __restrict__ corr, int b, size_t out_bstride, int pix,
+                                          int H1W1) const {
+    const Weights<T> w = bilin_weights<T>(bl);
+    // scalars: zeroing the struct's members instead costs corr_index_forward_coop<float, 3, true> a VGPR
+    work w00 = w.w00, w01 = w.w01, w10 = w.w10, w11 = w.w11;
+    if (!live) w00 = w01 = w10 = w11 = (work)0;
+    T* out = corr + (size_t)b * out_bstride + pix;
+    Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
+  }
+};
+
 template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(const T* __restrict__ volume,
                                                                  const float* __restrict__ coords,
@@ -227,39 +297,32 @@ __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(con
                                                                  int H2, int W2, size_t vol_elems,
                                                                  size_t out_bstride, float cscale,
                                                                  const int64_t* __restrict__ slots, long long cap) {
-  typedef typename Elem<T>::work work;
-  constexpr int RD = 2 * R + 1, NT = RD + 1;
+  typedef Lookup<T, R, SLOTTED> Q;
+  typedef typename Q::work work;
+  constexpr int NT = Q::NT;
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (pix >= H1W1) return;
-  const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale;
-  const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale;
-  size_t slot = (size_t)b;
-  bool live = true;
-  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
-  const Bilin bl = bilin_setup(x0, y0, R);
-  const T* plane = volume + (slot * H1W1 + pix) * ((size_t)H2 * W2);
+  Q q(slots, cap, b);
+  q.locate(coords, b, pix, H1W1, W2, cscale);
+  const T* plane = volume + (q.slot * H1W1 + pix) * ((size_t)H2 * W2);
   const uintptr_t vbeg = reinterpret_cast<uintptr_t>(volume);
   const uintptr_t vend = vbeg + vol_elems * sizeof(T);
-  // any tap of the window inside the plane at all?
-  const bool xany = live && (bl.x1 + NT > 0) && (bl.x1 < W2);
-
   work tap[NT][NT];  // [row j (y)][col i (x)]
 #pragma unroll
   for (int j = 0; j < NT; j++) {
-    const int y1 = bl.y1 + j;
-    const bool rowok = xany && (y1 >= 0) && (y1 < H2);
+    const int y1 = q.bl.y1 + j;
+    const bool rowok = q.xany && (y1 >= 0) && (y1 < H2);
 #pragma unroll
     for (int i = 0; i < NT; i++) tap[j][i] = (work)0;
     if (rowok) {
-      const T* rp = plane + (ptrdiff_t)y1 * W2 + bl.x1;
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(rp) & ~uintptr_t(3);
-      if (a0 >= vbeg && a0 + RowLoad<T, NT>::span_bytes() <= vend) {
+      const T* rp = plane + (ptrdiff_t)y1 * W2 + q.bl.x1;
+      if (row_load_ok<T, NT>(rp, vbeg, vend)) {
         RowLoad<T, NT>::load(rp, tap[j]);
       } else {  // first / last elements of the whole tensor only
 #pragma unroll 1
         for (int i = 0; i < NT; i++) {
-          const int x1 = bl.x1 + i;
+          const int x1 = q.bl.x1 + i;
           const work v = (x1 >= 0 && x1 < W2) ? Elem<T>::load(rp + i) : (work)0;
 #pragma unroll
           for (int i2 = 0; i2 < NT; i2++)
@@ -268,20 +331,12 @@ __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(con
       }
 #pragma unroll
       for (int i = 0; i < NT; i++) {
-        const int x1 = bl.x1 + i;
+        const int x1 = q.bl.x1 + i;
         if (x1 < 0 || x1 >= W2) tap[j][i] = (work)0;
       }
     }
   }
-  const float one = 1.0f;
-  // weights rounded to the element type (ck:55-65)
-  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )
-  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
-  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
-  T* out = corr + (size_t)b * out_bstride + pix;
-  Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
+  q.combine(tap, corr, b, out_bstride, pix, H1W1);
 }
 
 // Small planes (pyramid level 3 at 48x64: 96 bytes per query in fp16, 192 in fp32): the planes of the 64 queries of a wave
@@ -300,18 +355,17 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
                                                                T* __restrict__ corr, int H1W1, int H2, int W2,
                                                                size_t out_bstride, float cscale,
                                                                const int64_t* __restrict__ slots, long long cap) {
-  typedef typename Elem<T>::work work;
-  constexpr int RD = 2 * R + 1, NT = RD + 1;
+  typedef Lookup<T, R, SLOTTED> Q;
+  typedef typename Q::work work;
+  constexpr int NT = Q::NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x;
   const int pix0 = blockIdx.x * 64, b = blockIdx.y;
   const int nq = min(64, H1W1 - pix0);
   const int PB = H2 * W2 * (int)sizeof(T);      // bytes per plane: a multiple of 16 (checked by the launcher)
   const int pitch = PB + 4;
-  size_t slot = (size_t)b;
-  bool live = true;
-  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
-  const unsigned char* src = reinterpret_cast<const unsigned char*>(volume + (slot * H1W1 + pix0) * ((size_t)H2 * W2));
+  Q q(slots, cap, b);
+  const unsigned char* src = reinterpret_cast<const unsigned char*>(volume + (q.slot * H1W1 + pix0) * ((size_t)H2 * W2));
   const int nvec = (nq * PB) >> 4;
   for (int u = lane; u < nvec; u += 64) {
     const uint4 v = *reinterpret_cast<const uint4*>(src + (size_t)u * 16);
@@ -322,30 +376,21 @@ __global__ __launch_bounds__(64) void corr_index_forward_small(const T* __restri
   __syncthreads();
   if (lane >= nq) return;
   const int pix = pix0 + lane;
-  const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale;
-  const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale;
-  const Bilin bl = bilin_setup(x0, y0, R);
+  q.locate(coords, b, pix, H1W1, W2, cscale);
   const T* plane = reinterpret_cast<const T*>(smem + lane * pitch);
-  work tap[NT][NT];  // [row j (y)][col i (x)]
+  work tap[NT][NT];  // [row j (y)][col i (x)]: the whole plane is in LDS, every tap is its own guarded read
 #pragma unroll
   for (int j = 0; j < NT; j++) {
-    const int y1 = bl.y1 + j;
-    const bool rowok = live && (y1 >= 0) && (y1 < H2);
+    const int y1 = q.bl.y1 + j;
+    const bool rowok = q.live && (y1 >= 0) && (y1 < H2);
 #pragma unroll
     for (int i = 0; i < NT; i++) {
-      const int x1 = bl.x1 + i;
+      const int x1 = q.bl.x1 + i;
       const bool ok = rowok && x1 >= 0 && x1 < W2;
       tap[j][i] = ok ? Elem<T>::load(plane + (ok ? y1 * W2 + x1 : 0)) : (work)0;
     }
   }
-  const float one = 1.0f;
-  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
-  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
-  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
-  T* out = corr + (size_t)b * out_bstride + pix;
-  Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
+  q.combine(tap, corr, b, out_bstride, pix, H1W1);
 }
 
 template <typename T, int R, bool SLOTTED>
@@ -366,20 +411,17 @@ static bool launch_corr_small(const T* v, const float* coords, T* c, int B, int 
 // lanes of ONE instruction and the memory pipeline merges them into the 2-5 lines they occupy: every line is requested once
 // per query.  The rows travel through a wave-private LDS image [query][row][dwords] (pitch odd: conflict-free both ways) to
 // the lane that owns the query; arithmetic, rounding points and output layout are those of corr_index_forward_kernel.
-template <typename T, int NT> struct RowWords;   // dwords a row load brings (RowLoad) and the taps' place in them
-template <int NT> struct RowWords<__half, NT> { static constexpr int NW = RowLoad<__half, NT>::NW; };
-template <int NT> struct RowWords<float, NT> { static constexpr int NW = NT; };
-
 template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restrict__ volume,
                                                                const float* __restrict__ coords,
                                                                T* __restrict__ corr, int H1W1, int H2, int W2,
                                                                size_t vol_elems, size_t out_bstride, float cscale,
                                                                const int64_t* __restrict__ slots, long long cap) {
-  typedef typename Elem<T>::work work;
-  constexpr int RD = 2 * R + 1, NT = RD + 1;
+  typedef Lookup<T, R, SLOTTED> Q;
+  typedef typename Q::work work;
+  constexpr int NT = Q::NT;
   static_assert(NT == 8, "eight window rows <-> eight lanes per query");
-  constexpr int NW = RowWords<T, NT>::NW;
+  constexpr int NW = RowLoad<T, NT>::NW;
   constexpr bool HALF = sizeof(T) == 2;
   // image row: half -- the 8 taps themselves (the loader shifts an odd-aligned row into place): 4 dwords, 16-byte LDS
   // accesses, query pitch 36 dwords (9.2 KB per wave: 16 waves per CU); float -- the 8 dwords as loaded, pitch 65
@@ -391,30 +433,23 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
   const int pix = pix0 + lane;
   const int b = blockIdx.y;
   const bool valid = pix < H1W1;
-  const int cpix = valid ? pix : H1W1 - 1;
-  const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + cpix] * cscale;
-  const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + cpix] * cscale;
-  size_t slot = (size_t)b;
-  bool live = true;
-  if constexpr (SLOTTED) live = slot_of(slots, b, cap, &slot);
-  const Bilin bl = bilin_setup(x0, y0, R);
+  Q qr(slots, cap, b);
+  qr.locate(coords, b, valid ? pix : H1W1 - 1, H1W1, W2, cscale, valid);
   const uintptr_t vbeg = reinterpret_cast<uintptr_t>(volume);
   const uintptr_t vend = vbeg + vol_elems * sizeof(T);
   const size_t plane_elems = (size_t)H2 * W2;
-  const bool xany = valid && live && (bl.x1 + NT > 0) && (bl.x1 < W2);
   // ---- cooperative loads: pass `it` serves queries 8 it .. 8 it + 7
   const int lq = lane >> 3, lj = lane & 7;
 #pragma unroll
   for (int it = 0; it < 8; it++) {
     const int q = 8 * it + lq;
-    const int qx1 = __shfl(bl.x1, q), qy1 = __shfl(bl.y1, q);
-    const bool qany = __shfl((int)xany, q) != 0;
+    const int qx1 = __shfl(qr.bl.x1, q), qy1 = __shfl(qr.bl.y1, q);
+    const bool qany = __shfl((int)qr.xany, q) != 0;
     const int y1 = qy1 + lj;
     if (qany && y1 >= 0 && y1 < H2) {
-      const T* rp = volume + (slot * H1W1 + (pix0 + q)) * plane_elems + (ptrdiff_t)y1 * W2 + qx1;
-      const uintptr_t a0 = reinterpret_cast<uintptr_t>(rp) & ~uintptr_t(3);
-      if (a0 >= vbeg && a0 + NW * 4 <= vend) {   // (rows at the two ends of the tensor: the owner loads them itself)
-        const u32a4* src = reinterpret_cast<const u32a4*>(a0);
+      const T* rp = volume + (qr.slot * H1W1 + (pix0 + q)) * plane_elems + (ptrdiff_t)y1 * W2 + qx1;
+      if (row_load_ok<T, NT>(rp, vbeg, vend)) {   // (rows at the two ends of the tensor: the owner loads them itself)
+        const u32a4* src = reinterpret_cast<const u32a4*>(reinterpret_cast<uintptr_t>(rp) & ~uintptr_t(3));
         uint32_t w[NW];
 #pragma unroll
         for (int k = 0; k < NW; k++) w[k] = src[k];
@@ -438,19 +473,17 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
   __builtin_amdgcn_wave_barrier();
   if (!valid) return;
   // ---- the owner of the query collects its window
-  const T* plane = volume + (slot * H1W1 + pix) * plane_elems;
+  const T* plane = volume + (qr.slot * H1W1 + pix) * plane_elems;
   work tap[NT][NT];  // [row j (y)][col i (x)]
 #pragma unroll
   for (int j = 0; j < NT; j++) {
-    const int y1 = bl.y1 + j;
-    const bool rowok = xany && (y1 >= 0) && (y1 < H2);
+    const int y1 = qr.bl.y1 + j;
+    const bool rowok = qr.xany && (y1 >= 0) && (y1 < H2);
 #pragma unroll
     for (int i = 0; i < NT; i++) tap[j][i] = (work)0;
     if (rowok) {
-      const T* rp = plane + (ptrdiff_t)y1 * W2 + bl.x1;
-      const uintptr_t a = reinterpret_cast<uintptr_t>(rp);
-      const uintptr_t a0 = a & ~uintptr_t(3);
-      if (a0 >= vbeg && a0 + NW * 4 <= vend) {
+      const T* rp = plane + (ptrdiff_t)y1 * W2 + qr.bl.x1;
+      if (row_load_ok<T, NT>(rp, vbeg, vend)) {   // the loaders' test: this row is in the image
         const uint32_t* d = img + lane * PQ + j * RW;
         if constexpr (HALF) {
           const uint4 v4 = *reinterpret_cast<const uint4*>(d);
@@ -467,7 +500,7 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
       } else {  // first / last elements of the whole tensor only
 #pragma unroll 1
         for (int i = 0; i < NT; i++) {
-          const int x1 = bl.x1 + i;
+          const int x1 = qr.bl.x1 + i;
           const work v = (x1 >= 0 && x1 < W2) ? Elem<T>::load(rp + i) : (work)0;
 #pragma unroll
           for (int i2 = 0; i2 < NT; i2++)
@@ -476,19 +509,12 @@ __global__ __launch_bounds__(256) void corr_index_forward_coop(const T* __restri
       }
 #pragma unroll
       for (int i = 0; i < NT; i++) {
-        const int x1 = bl.x1 + i;
+        const int x1 = qr.bl.x1 + i;
         if (x1 < 0 || x1 >= W2) tap[j][i] = (work)0;
       }
     }
   }
-  const float one = 1.0f;
-  work w00 = Elem<T>::round((work)f32_value((one - bl.dx) * (one - bl.dy)));  // tap (a  ,c  )   ck:55-65
-  work w01 = Elem<T>::round((work)f32_value((one - bl.dx) * bl.dy));          // tap (a  ,c+1)
-  work w10 = Elem<T>::round((work)f32_value(bl.dx * (one - bl.dy)));          // tap (a+1,c  )
-  work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));                  // tap (a+1,c+1)
-  if (!live) w00 = w01 = w10 = w11 = (work)0;   // SLOTTED only: a slot outside the buffer
-  T* out = corr + (size_t)b * out_bstride + pix;
-  Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
+  qr.combine(tap, corr, b, out_bstride, pix, H1W1);
 }
 
 // rows of at most 64 bytes (two or more window rows per 128-byte line), radius 3, half / float
@@ -524,42 +550,46 @@ __global__ __launch_bounds__(256) void corr_index_forward_generic(const T* __res
     if (x1 < 0 || x1 >= W2 || y1 < 0 || y1 >= H2) return (work)0;
     return Elem<T>::load(plane + (size_t)y1 * W2 + x1);
   };
-  const work w00 = Elem<T>::round((work)f32_value((1.0f - bl.dx) * (1.0f - bl.dy)));
-  const work w01 = Elem<T>::round((work)f32_value((1.0f - bl.dx) * bl.dy));
-  const work w10 = Elem<T>::round((work)f32_value(bl.dx * (1.0f - bl.dy)));
-  const work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));
+  const Weights<T> w = bilin_weights<T>(bl);
   T* out = corr + (size_t)b * rd * rd * H1W1 + pix;
   for (int a = 0; a < rd; a++)
     for (int c = 0; c < rd; c++) {
-      work acc = Elem<T>::mul(tapv(a, c), w00);
-      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a, c + 1), w01));
-      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a + 1, c), w10));
-      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a + 1, c + 1), w11));
+      work acc = Elem<T>::mul(tapv(a, c), w.w00);
+      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a, c + 1), w.w01));
+      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a + 1, c), w.w10));
+      acc = Elem<T>::add(acc, Elem<T>::mul(tapv(a + 1, c + 1), w.w11));
       Elem<T>::store(out + (size_t)(a * rd + c) * H1W1, acc);
     }
 }
 
+// One level of a lookup at radius 3 or 4: small planes through LDS, else cooperative row loads, else per-lane row loads.
+// tests/corr_cases.py::volume_path restates this decision.
+template <typename T, bool SLOTTED>
+static void launch_lookup_level(const T* v, const float* coords, T* c, int B, int HW, int H2, int W2, size_t vol_elems,
+                                size_t obs, float cs, const int64_t* slots, long long cap, int r, hipStream_t s) {
+  with_radius(r, [&](auto rc) {
+    constexpr int R = decltype(rc)::value;
+    if (launch_corr_small<T, R, SLOTTED>(v, coords, c, B, HW, H2, W2, obs, cs, slots, cap, s)) return;
+    if (launch_corr_coop<T, R, SLOTTED>(v, coords, c, B, HW, H2, W2, vol_elems, obs, cs, slots, cap, s)) return;
+    hipLaunchKernelGGL((corr_index_forward_kernel<T, R, SLOTTED>), dim3((HW + 255) / 256, B), dim3(256), 0, s, v, coords, c,
+                       HW, H2, W2, vol_elems, obs, cs, slots, cap);
+  });
+}
+
+// The reference's operator: a one-level pyramid with unscaled coordinates and slot = batch index; other radii than 3 and
+// 4 take the generic kernel.
 template <typename T>
 static int corr_index_forward_t(const void* volume, const float* coords, void* corr, int B, int H1,
                                 int W1, int H2, int W2, int r, hipStream_t s) {
   const int HW = H1 * W1;
-  dim3 grid((HW + 255) / 256, B), block(256);
   const T* v = static_cast<const T*>(volume);
   T* c = static_cast<T*>(corr);
-  const size_t vol_elems = (size_t)B * HW * H2 * W2;
-  const size_t obs = (size_t)(2 * r + 1) * (2 * r + 1) * HW;
-  const int64_t* const ident = nullptr;   // slot = batch index
-  if (r == 3 && launch_corr_small<T, 3, false>(v, coords, c, B, HW, H2, W2, obs, 1.0f, ident, 0, s)) return 0;
-  if (r == 4 && launch_corr_small<T, 4, false>(v, coords, c, B, HW, H2, W2, obs, 1.0f, ident, 0, s)) return 0;
-  if (r == 3 && launch_corr_coop<T, 3, false>(v, coords, c, B, HW, H2, W2, vol_elems, obs, 1.0f, ident, 0, s)) return 0;
-  if (r == 3)
-    hipLaunchKernelGGL((corr_index_forward_kernel<T, 3, false>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs,
-                       1.0f, ident, 0LL);
-  else if (r == 4)
-    hipLaunchKernelGGL((corr_index_forward_kernel<T, 4, false>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems, obs,
-                       1.0f, ident, 0LL);
+  if (r == 3 || r == 4)
+    launch_lookup_level<T, false>(v, coords, c, B, HW, H2, W2, (size_t)B * HW * H2 * W2,
+                                  (size_t)(2 * r + 1) * (2 * r + 1) * HW, 1.0f, nullptr, 0, r, s);
   else
-    hipLaunchKernelGGL((corr_index_forward_generic<T>), grid, block, 0, s, v, coords, c, HW, H2, W2, r);
+    hipLaunchKernelGGL((corr_index_forward_generic<T>), dim3((HW + 255) / 256, B), dim3(256), 0, s, v, coords, c, HW, H2, W2,
+                       r);
   return 0;
 }
 
@@ -584,23 +614,13 @@ template <typename T, bool SLOTTED>
 static int corr_pyramid_forward_t(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
                                   void* corr, int B, int H1, int W1, int r, int levels, hipStream_t s) {
   const int HW = H1 * W1, rd2 = (2 * r + 1) * (2 * r + 1);
-  dim3 grid((HW + 255) / 256, B), block(256);
   const size_t obs = (size_t)levels * rd2 * HW;
   for (int l = 0; l < levels; l++) {
     const int H2 = H1 >> l, W2 = W1 >> l;
     const T* v = static_cast<const T*>(volumes[l]);
     T* c = static_cast<T*>(corr) + (size_t)l * rd2 * HW;
     const size_t vol_elems = (size_t)(SLOTTED ? cap : (long long)B) * HW * H2 * W2;
-    const float cs = 1.0f / (float)(1 << l);
-    if (r == 3 && launch_corr_small<T, 3, SLOTTED>(v, coords, c, B, HW, H2, W2, obs, cs, slots, cap, s)) continue;
-    if (r == 4 && launch_corr_small<T, 4, SLOTTED>(v, coords, c, B, HW, H2, W2, obs, cs, slots, cap, s)) continue;
-    if (r == 3 && launch_corr_coop<T, 3, SLOTTED>(v, coords, c, B, HW, H2, W2, vol_elems, obs, cs, slots, cap, s)) continue;
-    if (r == 3)
-      hipLaunchKernelGGL((corr_index_forward_kernel<T, 3, SLOTTED>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems,
-                         obs, cs, slots, cap);
-    else
-      hipLaunchKernelGGL((corr_index_forward_kernel<T, 4, SLOTTED>), grid, block, 0, s, v, coords, c, HW, H2, W2, vol_elems,
-                         obs, cs, slots, cap);
+    launch_lookup_level<T, SLOTTED>(v, coords, c, B, HW, H2, W2, vol_elems, obs, 1.0f / (float)(1 << l), slots, cap, r, s);
   }
   return 0;
 }
@@ -647,23 +667,20 @@ __global__ __launch_bounds__(256) void corr_index_backward_kernel(const float* _
                                coords[((size_t)b * 2 + 1) * H1W1 + pix], r);
   T* plane = volume_grad + ((size_t)b * H1W1 + pix) * ((size_t)H2 * W2);
   const T* g = corr_grad + (size_t)b * rd * rd * H1W1 + pix;
-  const work w11 = Elem<T>::round((work)f32_value(bl.dx * bl.dy));
-  const work w10 = Elem<T>::round((work)f32_value(bl.dx * (1.0f - bl.dy)));
-  const work w01 = Elem<T>::round((work)f32_value((1.0f - bl.dx) * bl.dy));
-  const work w00 = Elem<T>::round((work)f32_value((1.0f - bl.dx) * (1.0f - bl.dy)));
+  const Weights<T> w = bilin_weights<T>(bl);
   for (int i = 0; i < rd + 1; i++)
     for (int j = 0; j < rd + 1; j++) {
       const int x1 = bl.x1 + i, y1 = bl.y1 + j;
       if (x1 < 0 || x1 >= W2 || y1 < 0 || y1 >= H2) continue;
       work acc = (work)0;  // ck:106-117, same order and rounding points
       if (i > 0 && j > 0)
-        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)((i - 1) * rd + (j - 1)) * H1W1), w11));
+        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)((i - 1) * rd + (j - 1)) * H1W1), w.w11));
       if (i > 0 && j < rd)
-        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)((i - 1) * rd + j) * H1W1), w10));
+        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)((i - 1) * rd + j) * H1W1), w.w10));
       if (i < rd && j > 0)
-        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)(i * rd + (j - 1)) * H1W1), w01));
+        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)(i * rd + (j - 1)) * H1W1), w.w01));
       if (i < rd && j < rd)
-        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)(i * rd + j) * H1W1), w00));
+        acc = Elem<T>::add(acc, Elem<T>::mul(Elem<T>::load(g + (size_t)(i * rd + j) * H1W1), w.w00));
       Elem<T>::store(plane + (size_t)y1 * W2 + x1, acc);
     }
 }
@@ -987,25 +1004,10 @@ __device__ unsigned long long g_am_stamps[768 * 4 * 32];
 #define AMNOTE(slot, v) do { } while (0)
 #endif
 constexpr int AM_TX = 16, AM_TY = 4;     // query tile of a workgroup
-// Input element type of the matrix-core path.  A stage is 64 bytes per position whatever the type, so the LDS
-// image, the swizzle and the DMA plan are shared: fp32 = 16 channels per stage on v_mfma_f32_16x16x4_f32 (4 k-steps
-// per stage), fp16 = 32 channels per stage on ONE v_mfma_f32_16x16x32_f16 (16x the fp32 matrix rate; products of
-// two halves are exact in fp32, accumulation is fp32, so the half path reproduces the reference's
-// `.float()` evaluation of half feature maps -- modules/corr.py:120 -- up to summation order).
-template <typename TI> struct AmIn;
-template <> struct AmIn<float> {
-  static constexpr int EPC = 4;            // elements per 16-byte chunk
-  static constexpr int CH = 16;            // channels per stage
-  static constexpr int MAXSTAGE = 8;       // C <= 128 on this path
-};
-template <> struct AmIn<__half> {
-  static constexpr int EPC = 8;
-  static constexpr int CH = 32;
-  static constexpr int MAXSTAGE = 4;       // C <= 128
-};
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void am_store(float* p, float v) { *p = v; }
-__device__ __forceinline__ void am_store(__half* p, float v) { *p = __float2half_rn(v); }
+// A stage is 64 bytes per position: 16 fp32 channels on v_mfma_f32_16x16x4_f32, 4 k-steps per stage.  fp32 maps only:
+// half maps take altcorr_wave_f16 below.
+constexpr int AM_CH = 16;                // channels per stage
+constexpr int AM_MAXSTAGE = 8;           // C <= 128 on this path
 constexpr int AM_MAXBLK = 15;            // 16-position blocks per wave (240 positions >= 15x16)
 // D exchange: r=3 keeps 12 blocks per round (50 KB of LDS, 3 workgroups per CU; a second round serves
 // blocks 13..15 of strongly diverging windows); r=4 windows need 13+ blocks even for a smooth flow
@@ -1033,14 +1035,12 @@ __device__ __forceinline__ int wave_max16(int v) {
 // Body shared by the two entry points below.  f1e / f2b: feature maps of this edge (channels last),
 // cbase: its query coordinates, multiplied by cscale (1, or 2^-level for the pyramid entry point:
 // exact), oute: its (2r+1)^2 output planes, tile: index of the 16x4 query tile.
-template <int R, typename TI, typename TO>
-__device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, const TI* __restrict__ f2b,
+template <int R>
+__device__ __forceinline__ void altcorr_mfma_body(const float* __restrict__ f1e, const float* __restrict__ f2b,
                                                   const float* __restrict__ cbase, const float cscale,
-                                                  TO* __restrict__ oute, const int tile, const int H1,
+                                                  float* __restrict__ oute, const int tile, const int H1,
                                                   const int W1, const int H2, const int W2, const int C) {
   constexpr int RD = 2 * R + 1, NT = RD + 1;
-  constexpr int AM_CH = AmIn<TI>::CH, AM_EPC = AmIn<TI>::EPC, AM_MAXSTAGE = AmIn<TI>::MAXSTAGE;
-  constexpr bool HALF_IN = AM_EPC == 8;
   constexpr int AM_XBLK = AmCfg<R>::XBLK, AM_CP = AmCfg<R>::CP, AM_LDS_FLOATS = AmCfg<R>::LDS_FLOATS;
   static_assert(AM_MAXPOS * 16 <= AM_LDS_FLOATS, "one stage (64 bytes per position) of the largest box must fit");
   __shared__ __attribute__((aligned(16))) float lds[AM_LDS_FLOATS];
@@ -1064,7 +1064,7 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
   float2 gc = *reinterpret_cast<const float2*>(cbase + 2 * gpix);
   f4 a_all[AM_MAXSTAGE];  // this lane's A fragments of all stages: channels 16 st + 4g .. +3 of its query
   {
-    const TI* f1p = f1e + (size_t)gpix * C + AM_EPC * g;
+    const float* f1p = f1e + (size_t)gpix * C + 4 * g;
 #pragma unroll
     for (int st = 0; st < AM_MAXSTAGE; st++)
       a_all[st] = *reinterpret_cast<const f4*>(f1p + min(st * AM_CH, C - AM_CH));  // stages >= C/16 are never used
@@ -1109,12 +1109,12 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
   const Bilin obl = bilin_setup(cbase[2 * opix] * cscale, cbase[2 * opix + 1] * cscale, R);            \
   const float wnw = f32_value(obl.dy * obl.dx), wne = f32_value(obl.dy * (1.0f - obl.dx));             \
   const float wsw = f32_value((1.0f - obl.dy) * obl.dx), wse = f32_value((1.0f - obl.dy) * (1.0f - obl.dx)); \
-  TO* out = oute + opix;   /* weights: ak:119-122 */
+  float* out = oute + opix;   /* weights: ak:119-122 */
 
   if (!fits) {  // incoherent tile: per-query direct evaluation
     if (!ook) return;
     AM_OUT_ROLE
-    const TI* f1 = f1e + (size_t)opix * C;
+    const float* f1 = f1e + (size_t)opix * C;
     for (int o = og; o < RD * RD; o += 4) {
       const int ox = o / RD, oy = o % RD;
       float s4[4];
@@ -1122,18 +1122,10 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
         const int h2 = obl.y1 + oy + (t >> 1), w2 = obl.x1 + ox + (t & 1);
         float s = 0.f;
         if (h2 >= 0 && h2 < H2 && w2 >= 0 && w2 < W2) {
-          const TI* f2 = f2b + ((size_t)h2 * W2 + w2) * C;
-          if constexpr (HALF_IN) {
-            for (int c = 0; c < C; c += 8) {
-              const h8 u = *reinterpret_cast<const h8*>(f1 + c), v = *reinterpret_cast<const h8*>(f2 + c);
-#pragma unroll
-              for (int k = 0; k < 8; k++) s = fmaf((float)u[k], (float)v[k], s);
-            }
-          } else {
-            for (int c = 0; c < C; c += 4) {
-              const f4 u = *reinterpret_cast<const f4*>(f1 + c), v = *reinterpret_cast<const f4*>(f2 + c);
-              s = fmaf(u[0], v[0], s); s = fmaf(u[1], v[1], s); s = fmaf(u[2], v[2], s); s = fmaf(u[3], v[3], s);
-            }
+          const float* f2 = f2b + ((size_t)h2 * W2 + w2) * C;
+          for (int c = 0; c < C; c += 4) {
+            const f4 u = *reinterpret_cast<const f4*>(f1 + c), v = *reinterpret_cast<const f4*>(f2 + c);
+            s = fmaf(u[0], v[0], s); s = fmaf(u[1], v[1], s); s = fmaf(u[2], v[2], s); s = fmaf(u[3], v[3], s);
           }
         }
         s4[t] = s;
@@ -1142,7 +1134,7 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
       acc = acc + s4[1] * wsw;
       acc = acc + s4[2] * wne;
       acc = acc + s4[3] * wnw;
-      am_store(out + (size_t)o * H1W1, acc);
+      out[(size_t)o * H1W1] = acc;
     }
     return;
   }
@@ -1165,18 +1157,18 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
   for (int it = 0; it < AM_MAXSLOT; it++) {
     const int P = min(16 * (wave + 4 * it) + (lane >> 2), max(npos - 1, 0));  // pad lanes re-read the last row
     const int yy = (int)(((float)P + 0.5f) * rbw), xx = P - yy * BW;  // exact: P < 1024, BW < 1024
-    soff[it] = ((by0 + yy) * W2 + (bx0 + xx)) * C + AM_EPC * ((lane & 3) ^ ((lane >> 3) & 3));
+    soff[it] = ((by0 + yy) * W2 + (bx0 + xx)) * C + 4 * ((lane & 3) ^ ((lane >> 3) & 3));
   }
   const unsigned lds_base = (unsigned)(size_t)((__attribute__((address_space(3))) float*)lds);
   auto issue_stage = [&](int stage, int slot) {
-    const TI* src = f2b + stage * AM_CH;
+    const float* src = f2b + stage * AM_CH;
     const unsigned dst0 = lds_base + 4u * (unsigned)(slot * slot_floats);
 #pragma unroll
     for (int it = 0; it < AM_MAXSLOT; it++) {
       const int k = wave + 4 * it;
       if (k < nk) {  // wave-uniform
         const unsigned dst = __builtin_amdgcn_readfirstlane(dst0 + 4u * (unsigned)(k * 256));
-        const TI* gsrc = src + soff[it];
+        const float* gsrc = src + soff[it];
         unsigned keep;
         asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                      : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
@@ -1248,18 +1240,11 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
           const f4 b1 = *reinterpret_cast<const f4*>(bs + boff[3 * grp + 1]);
           const f4 b2 = *reinterpret_cast<const f4*>(bs + boff[3 * grp + 2]);
           f4 c0 = acc[3 * grp], c1 = acc[3 * grp + 1], c2 = acc[3 * grp + 2];
-          if constexpr (HALF_IN) {  // lane group g holds k = 8g .. 8g+7 of both operands: one instruction per stage
-            const h8 ah = __builtin_bit_cast(h8, a);
-            c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(h8, b0), c0, 0, 0, 0);
-            c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(h8, b1), c1, 0, 0, 0);
-            c2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, __builtin_bit_cast(h8, b2), c2, 0, 0, 0);
-          } else {
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-              c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b0[e], c0, 0, 0, 0);
-              c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b1[e], c1, 0, 0, 0);
-              c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b2[e], c2, 0, 0, 0);
-            }
+          for (int e = 0; e < 4; e++) {
+            c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b0[e], c0, 0, 0, 0);
+            c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b1[e], c1, 0, 0, 0);
+            c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b2[e], c2, 0, 0, 0);
           }
           acc[3 * grp] = c0; acc[3 * grp + 1] = c1; acc[3 * grp + 2] = c2;
         }
@@ -1339,13 +1324,13 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
     if (!ook) return;
 #pragma unroll
     for (int m = 0; m < NOUT; m++)
-      if (og + 4 * m < RD * RD) am_store(out + (size_t)(og + 4 * m) * H1W1, vacc[m]);
+      if (og + 4 * m < RD * RD) out[(size_t)(og + 4 * m) * H1W1] = vacc[m];
   } else if (__all(inside)) {
     AMNOTE(11, 1);
     if (!ook) return;
     for (int ox = og; ox < RD; ox += 4) {
       const float* dp = dq + ry * osw + rx + ox;
-      TO* op = out + (size_t)ox * RD * H1W1;
+      float* op = out + (size_t)ox * RD * H1W1;
       float t0 = dp[0], t1 = dp[1];
 #pragma unroll
       for (int oy = 0; oy < RD; oy++) {
@@ -1355,7 +1340,7 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
         v = v + t1 * wsw;     // tap (oy  , ox+1)
         v = v + u0 * wne;     // tap (oy+1, ox  )
         v = v + u1 * wnw;     // tap (oy+1, ox+1)
-        am_store(op + (size_t)oy * H1W1, v);
+        op[(size_t)oy * H1W1] = v;
         t0 = u0; t1 = u1;
       }
     }
@@ -1366,7 +1351,7 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
       const int xa = rx + ox, xb = xa + 1;
       const bool ina = xa >= 0 && xa < osw, inb = xb >= 0 && xb < osw;
       const int xac = min(max(xa, 0), xmax), xbc = min(max(xb, 0), xmax);
-      TO* op = out + (size_t)ox * RD * H1W1;
+      float* op = out + (size_t)ox * RD * H1W1;
       float t0 = 0.f, t1 = 0.f;
 #pragma unroll
       for (int j = 0; j < NT; j++) {
@@ -1381,7 +1366,7 @@ __device__ __forceinline__ void altcorr_mfma_body(const TI* __restrict__ f1e, co
           v = v + t1 * wsw;
           v = v + u0 * wne;
           v = v + u1 * wnw;
-          am_store(op + (size_t)(j - 1) * H1W1, v);
+          op[(size_t)(j - 1) * H1W1] = v;
         }
         t0 = u0; t1 = u1;
       }
@@ -1403,11 +1388,11 @@ __device__ __forceinline__ unsigned am_virtual_id() {
 }
 
 // altcorr_forward (ak:27-142): grid (tiles, N, B)
-template <int R, typename TI, typename TO>
-__global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_forward_mfma(const TI* __restrict__ fmap1,
-                                                               const TI* __restrict__ fmap2,
+template <int R>
+__global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_forward_mfma(const float* __restrict__ fmap1,
+                                                               const float* __restrict__ fmap2,
                                                                const float* __restrict__ coords,
-                                                               TO* __restrict__ corr, int N, int H1,
+                                                               float* __restrict__ corr, int N, int H1,
                                                                int W1, int H2, int W2, int C) {
   constexpr int RD = 2 * R + 1;
   const unsigned v = am_virtual_id();
@@ -1415,7 +1400,7 @@ __global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_forward_mfma(co
   const unsigned e = v / gridDim.x;
   const int n = (int)(e % gridDim.y), b = (int)(e / gridDim.y);
   const size_t H1W1 = (size_t)H1 * W1;
-  altcorr_mfma_body<R, TI, TO>(fmap1 + (size_t)b * H1W1 * C, fmap2 + (size_t)b * H2 * W2 * C,
+  altcorr_mfma_body<R>(fmap1 + (size_t)b * H1W1 * C, fmap2 + (size_t)b * H2 * W2 * C,
                        coords + ((size_t)b * N + n) * H1W1 * 2, 1.0f,
                        corr + (((size_t)b * N + n) * RD * RD) * H1W1, tile, H1, W1, H2, W2, C);
 }
@@ -1451,7 +1436,7 @@ __global__ __launch_bounds__(256, AmCfg<R>::MIN_WG) void altcorr_pyramid_mfma(Al
     return;
   }
   const float* lp = lvl == 0 ? pyr.level[0] : (lvl == 1 ? pyr.level[1] : (lvl == 2 ? pyr.level[2] : pyr.level[3]));
-  altcorr_mfma_body<R, float, float>(pyr.level[0] + (size_t)fi * H1W1 * C, lp + (size_t)fj * H2 * W2 * C,
+  altcorr_mfma_body<R>(pyr.level[0] + (size_t)fi * H1W1 * C, lp + (size_t)fj * H2 * W2 * C,
                        coords + (size_t)e * H1W1 * 2, 1.0f / (float)(1 << lvl), oute, tile, H1, W1, H2, W2, C);
 }
 
@@ -1491,6 +1476,9 @@ __device__ __forceinline__ int row_max16(int v) {
   v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
   return v;
 }
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void am_store(float* p, float v) { *p = v; }   // fp32 output: the fused pyramid entry
+__device__ __forceinline__ void am_store(__half* p, float v) { *p = __float2half_rn(v); }
 template <int R> struct AwCfg {
   static constexpr int MAXBLK = (R <= 3) ? 15 : 20;   // 16-position blocks per wave box (r=4 windows are 10x10)
   static constexpr int CP = 16 * MAXBLK + 4;          // D pitch in floats (== 4 mod 32)
@@ -1737,14 +1725,15 @@ template <typename TO>
 static int launch_altcorr_wave_f16(const AwArgs& a, int r, int units, hipStream_t s) {
   const int tiles = ((a.W1 + 3) / 4) * ((a.H1 + 3) / 4);
   dim3 grid(tiles, a.N, units), block(64);
-#define AW_LAUNCH(RR, NN) hipLaunchKernelGGL((altcorr_wave_f16<RR, NN, TO>), grid, block, 0, s, a)
-  const int nst = a.C / 32;
-  if (r == 3) {
-    if (nst == 4) AW_LAUNCH(3, 4); else if (nst == 3) AW_LAUNCH(3, 3); else if (nst == 2) AW_LAUNCH(3, 2); else AW_LAUNCH(3, 1);
-  } else {
-    if (nst == 4) AW_LAUNCH(4, 4); else if (nst == 3) AW_LAUNCH(4, 3); else if (nst == 2) AW_LAUNCH(4, 2); else AW_LAUNCH(4, 1);
-  }
-#undef AW_LAUNCH
+  with_radius(r, [&](auto rc) {
+    constexpr int R = decltype(rc)::value;
+    switch (a.C / 32) {  // k-steps
+      case 4: hipLaunchKernelGGL((altcorr_wave_f16<R, 4, TO>), grid, block, 0, s, a); break;
+      case 3: hipLaunchKernelGGL((altcorr_wave_f16<R, 3, TO>), grid, block, 0, s, a); break;
+      case 2: hipLaunchKernelGGL((altcorr_wave_f16<R, 2, TO>), grid, block, 0, s, a); break;
+      default: hipLaunchKernelGGL((altcorr_wave_f16<R, 1, TO>), grid, block, 0, s, a);
+    }
+  });
   return 0;
 }
 
@@ -1758,7 +1747,10 @@ template <typename T>
 static int altcorr_forward_t(const void* f1, const void* f2, const float* coords, void* corr, int B,
                              int N, int H1, int W1, int H2, int W2, int C, int r, hipStream_t s) {
   const int HW = H1 * W1;
-  dim3 grid((HW * 16 + 255) / 256, N, B), block(256);
+  // 16 lanes per query: HW * 16 leaves int from HW = 2^27, and the kernel's 32-bit thread index wraps from HW = 2^28
+  const long long gx = ((long long)HW * 16 + 255) / 256;
+  if (gx > (1LL << 24)) return DROID_E_ARG;
+  dim3 grid((unsigned)gx, N, B), block(256);
   hipLaunchKernelGGL((altcorr_forward_generic<T>), grid, block, 0, s, static_cast<const T*>(f1),
                      static_cast<const T*>(f2), coords, static_cast<T*>(corr), N, HW, H2, W2, C, r);
   return 0;
@@ -1768,19 +1760,18 @@ int launch_altcorr_forward(const void* f1, const void* f2, const float* coords, 
                            int N, int H1, int W1, int H2, int W2, int C, int r, int dtype,
                            hipStream_t s) {
   if (B > 65535 || N > 65535) return DROID_E_ARG;
-  if (dtype == DROID_F32 && (C % AmIn<float>::CH) == 0 && C <= AmIn<float>::CH * AmIn<float>::MAXSTAGE && (r == 3 || r == 4) &&
+  if (dtype == DROID_F32 && (C % AM_CH) == 0 && C <= AM_CH * AM_MAXSTAGE && (r == 3 || r == 4) &&
       (long)H2 * W2 * C < (1l << 30)) {
     const int tiles = ((W1 + AM_TX - 1) / AM_TX) * ((H1 + AM_TY - 1) / AM_TY);
-    dim3 grid(tiles, N, B), block(256);
-    if (r == 3)
-      hipLaunchKernelGGL((altcorr_forward_mfma<3, float, float>), grid, block, 0, s, static_cast<const float*>(f1),
-                         static_cast<const float*>(f2), coords, static_cast<float*>(corr), N, H1, W1, H2, W2, C);
-    else
-      hipLaunchKernelGGL((altcorr_forward_mfma<4, float, float>), grid, block, 0, s, static_cast<const float*>(f1),
-                         static_cast<const float*>(f2), coords, static_cast<float*>(corr), N, H1, W1, H2, W2, C);
+    with_radius(r, [&](auto rc) {
+      hipLaunchKernelGGL((altcorr_forward_mfma<decltype(rc)::value>), dim3(tiles, N, B), dim3(256), 0, s,
+                         static_cast<const float*>(f1), static_cast<const float*>(f2), coords, static_cast<float*>(corr), N,
+                         H1, W1, H2, W2, C);
+    });
     return 0;
   }
-  // half maps (altcorr_kernel.cu:308 dispatches half): f16 matrix cores, fp32 accumulation, half output
+  // half maps (altcorr_kernel.cu:308 dispatches half): f16 matrix cores, fp32 accumulation, half output.  Other half maps
+  // (channels no multiple of 32, or a map of 2^30 elements or more) take the generic kernel at the end
   if (dtype == DROID_F16 && (C % 32) == 0 && C <= 128 && (r == 3 || r == 4) && (long)H2 * W2 * C < (1l << 30) &&
       (long)H1 * W1 * C < (1l << 30)) {
     AwArgs a{};
@@ -1791,27 +1782,13 @@ int launch_altcorr_forward(const void* f1, const void* f2, const float* coords, 
     a.H2[0] = H2; a.W2[0] = W2; a.cscale[0] = 1.0f;
     return launch_altcorr_wave_f16<__half>(a, r, B, s);
   }
-  if (dtype == DROID_F16 && (C % AmIn<__half>::CH) == 0 && C <= AmIn<__half>::CH * AmIn<__half>::MAXSTAGE && (r == 3 || r == 4) &&
-      (long)H2 * W2 * C < (1l << 30)) {
-    const int tiles = ((W1 + AM_TX - 1) / AM_TX) * ((H1 + AM_TY - 1) / AM_TY);
-    dim3 grid(tiles, N, B), block(256);
-    if (r == 3)
-      hipLaunchKernelGGL((altcorr_forward_mfma<3, __half, __half>), grid, block, 0, s, static_cast<const __half*>(f1),
-                         static_cast<const __half*>(f2), coords, static_cast<__half*>(corr), N, H1, W1, H2, W2, C);
-    else
-      hipLaunchKernelGGL((altcorr_forward_mfma<4, __half, __half>), grid, block, 0, s, static_cast<const __half*>(f1),
-                         static_cast<const __half*>(f2), coords, static_cast<__half*>(corr), N, H1, W1, H2, W2, C);
-    return 0;
-  }
   if (dtype == DROID_F32 && (C % ALT_CH) == 0 && (r == 3 || r == 4)) {
     const int tiles = ((W1 + ALT_TQ - 1) / ALT_TQ) * ((H1 + ALT_TQ - 1) / ALT_TQ);
-    dim3 grid(tiles, N, B), block(ALT_THREADS);
-    if (r == 3)
-      hipLaunchKernelGGL((altcorr_forward_tiled<3>), grid, block, 0, s, static_cast<const float*>(f1),
-                         static_cast<const float*>(f2), coords, static_cast<float*>(corr), N, H1, W1, H2, W2, C);
-    else
-      hipLaunchKernelGGL((altcorr_forward_tiled<4>), grid, block, 0, s, static_cast<const float*>(f1),
-                         static_cast<const float*>(f2), coords, static_cast<float*>(corr), N, H1, W1, H2, W2, C);
+    with_radius(r, [&](auto rc) {
+      hipLaunchKernelGGL((altcorr_forward_tiled<decltype(rc)::value>), dim3(tiles, N, B), dim3(ALT_THREADS), 0, s,
+                         static_cast<const float*>(f1), static_cast<const float*>(f2), coords, static_cast<float*>(corr), N,
+                         H1, W1, H2, W2, C);
+    });
     return 0;
   }
   switch (dtype) {
@@ -1828,7 +1805,7 @@ int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t*
                                    const float* coords, float* corr, int E, int frames, int H, int W, int C,
                                    int r, int nlevels, int dtype, hipStream_t s) {
   if (dtype != DROID_F32 && dtype != DROID_F16) return DROID_E_ARG;
-  const int ch = dtype == DROID_F16 ? AmIn<__half>::CH : AmIn<float>::CH;
+  const int ch = dtype == DROID_F16 ? 32 : AM_CH;   // channels per k-step of altcorr_wave_f16 / per stage
   if (nlevels < 1 || nlevels > 4 || (r != 3 && r != 4) || (C % ch) != 0 || C > 128) return DROID_E_ARG;
   if ((H >> (nlevels - 1)) < 1 || (W >> (nlevels - 1)) < 1 || (long)H * W * C >= (1l << 30)) return DROID_E_ARG;
   if ((long)E * nlevels > 65535) return DROID_E_ARG;
@@ -1846,11 +1823,10 @@ int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t*
   AltPyramid pyr;
   for (int l = 0; l < 4; l++) pyr.level[l] = static_cast<const float*>(levels_dev[l < nlevels ? l : nlevels - 1]);
   const int tiles = ((W + AM_TX - 1) / AM_TX) * ((H + AM_TY - 1) / AM_TY);
-  dim3 grid(tiles, nlevels, E), block(256);
-  if (r == 3)
-    hipLaunchKernelGGL(altcorr_pyramid_mfma<3>, grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
-  else
-    hipLaunchKernelGGL(altcorr_pyramid_mfma<4>, grid, block, 0, s, pyr, ii, jj, coords, corr, frames, H, W, C);
+  with_radius(r, [&](auto rc) {
+    hipLaunchKernelGGL(altcorr_pyramid_mfma<decltype(rc)::value>, dim3(tiles, nlevels, E), dim3(256), 0, s, pyr, ii, jj, coords,
+                       corr, frames, H, W, C);
+  });
   return 0;
 }
 
@@ -2073,12 +2049,10 @@ int launch_altcorr_backward(const float* f1, const float* f2, const float* coord
   const int HW = H1 * W1;
   if ((C % AB_CH) == 0 && (r == 3 || r == 4)) {
     const int tiles = ((W1 + ABT - 1) / ABT) * ((H1 + ABT - 1) / ABT);
-    if (r == 3)
-      hipLaunchKernelGGL((altcorr_backward_tiled<3>), dim3(tiles, N, B), dim3(256), 0, s, f1, f2, coords, corr_grad, f1g,
-                         f2g, N, H1, W1, H2, W2, C);
-    else
-      hipLaunchKernelGGL((altcorr_backward_tiled<4>), dim3(tiles, N, B), dim3(256), 0, s, f1, f2, coords, corr_grad, f1g,
-                         f2g, N, H1, W1, H2, W2, C);
+    with_radius(r, [&](auto rc) {
+      hipLaunchKernelGGL((altcorr_backward_tiled<decltype(rc)::value>), dim3(tiles, N, B), dim3(256), 0, s, f1, f2, coords,
+                         corr_grad, f1g, f2g, N, H1, W1, H2, W2, C);
+    });
     return 0;
   }
   hipLaunchKernelGGL(altcorr_backward_kernel, dim3((HW * 16 + 255) / 256, N, B), dim3(256), 0, s, f1,

@@ -13,8 +13,8 @@ CS_MAXPLANE = 192
 ALT_TQ, ALT_MAXPOS, ALT_CH = 8, 448, 32
 AM_TX, AM_TY, AM_MAXBLK, AM_MAXPOS = 16, 4, 15, 640
 AM_XBLK = {3: 12, 4: 15}                 # AmCfg<R>::XBLK
-AM_CH = {"f32": 16, "f16": 32}           # AmIn<T>::CH
-AM_MAXSTAGE = {"f32": 8, "f16": 4}       # AmIn<T>::MAXSTAGE
+AM_CH = {"f32": 16}                      # AM_CH: the workgroup matrix-core path takes fp32 maps only
+AM_MAXSTAGE = {"f32": 8}                 # AM_MAXSTAGE
 AW_MAXBLK = {3: 15, 4: 20}               # AwCfg<R>::MAXBLK
 ABT, AB_CH, AB_MAXPOS = 8, 16, 448
 G1MAX = 16                               # altcorr_backward_kernel keeps 16 * G1MAX channels in registers
@@ -50,8 +50,6 @@ def alt_forward_path(dtype, r, C, H1, W1, H2, W2):
         return "mfma_f32"
     if dtype == "f16" and C % 32 == 0 and C <= 128 and r in (3, 4) and H2 * W2 * C < lim and H1 * W1 * C < lim:
         return "wave_f16"
-    if dtype == "f16" and C % AM_CH["f16"] == 0 and C <= AM_CH["f16"] * AM_MAXSTAGE["f16"] and r in (3, 4) and H2 * W2 * C < lim:
-        return "mfma_f16"   # only with a query map of 2^30 or more elements (2 GiB of halves): see DESIGN.md
     if dtype == "f32" and C % ALT_CH == 0 and r in (3, 4):
         return "tiled"
     return "generic"
