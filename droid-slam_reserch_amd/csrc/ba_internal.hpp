@@ -12,9 +12,10 @@ constexpr int LIN_CP = LIN_THREADS * LIN_PPT;    // pixels per workgroup chunk
 constexpr int CHOL_NB = 64;                      // Cholesky block size
 // row pitch of the augmented system in doubles: 128-byte rows, so 64-column tiles never share a cache line
 __host__ __device__ inline int chol_ld(int n) { return (n + 1 + 15) & ~15; }
-// ints of hand-off flags (done[], dver[], abort) of an n x n solve
+// ints of hand-off flags (done[block rows], dver[block rows], abort) of an n x n solve; what they mean: cfp_input (chol.hip)
 __host__ __device__ inline size_t chol_flag_words(int n) { return 2 * ((size_t)(n + 1 + CHOL_NB - 1) / CHOL_NB) + 8; }
-// lower-triangle tiles of the augmented system in column-major order: tile (bi, bj), bi >= bj
+// lower-triangle tiles of the augmented system in column-major order: tile (bi, bj), bi >= bj.  The same index is the
+// tile's owner (index mod grid) under both schedulers of the single-launch factorisation and its hand-over slot
 __host__ __device__ inline int chol_tile_index(int nrb, int bi, int bj) { return bj * nrb - bj * (bj - 1) / 2 + (bi - bj); }
 __host__ __device__ inline size_t chol_tiles(int n) {
   const int nb = (n + CHOL_NB - 1) / CHOL_NB, nrb = (n + 1 + CHOL_NB - 1) / CHOL_NB;
@@ -269,7 +270,7 @@ void launch_update(const BaView& v, float* poses, float* disps, const float* int
                    bool motion_only, hipStream_t s, int* status_mirror = nullptr);
 // The Cholesky solve of a CholSystem (chol.hip), damped: diag += ep + lm * diag.  launch_chol_solve = the preset
 // (unless done), launch_chol_factor, launch_chol_backsolve; launch_chol_factor returns whether the single-launch
-// kernel ran, and launch_chol_backsolve needs that answer.
+// kernel (chol_factor_persistent_kernel<false>: step-major scheduler) ran, and launch_chol_backsolve needs that answer.
 void launch_chol_preset(const CholSystem& c, hipStream_t s);
 bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s);
 void launch_chol_backsolve(const CholSystem& c, bool factor_single, hipStream_t s);
@@ -277,7 +278,8 @@ void launch_chol_solve(const CholSystem& c, double lm, double ep, hipStream_t s,
 
 // Overlap mode (multi-GPU): block columns [J0, J1) of the all-reduced packed system -> pitched matrix, damped; then
 // ready[J0..J1) = epoch for the factorisation that is already running.  launch_chol_factor_overlap starts that
-// single-launch factorisation (false: not available for this system); launch_chol_backsolve(c, true, s) follows it.
+// single-launch factorisation (chol_factor_persistent_kernel<true>: per-tile scheduler; false: not available for this
+// system, nothing was launched); launch_chol_backsolve(c, true, s) follows it.
 void launch_unpack_cols(const BaView& v, int J0, int J1, double lm, double ep, int epoch, hipStream_t s);
 bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s);
 

@@ -17,9 +17,11 @@
 //     inside the step) as 4 steps of {16x16 in-register wave factorisation with DPP-broadcast multipliers and an
 //     rsqrt+Newton pivot reciprocal, triangular solves as GEMMs with the block inverse, MFMA block updates} and
 //     solve their own tile against it;
-//   * `chol_factor_persistent_kernel`: the whole factorisation in ONE launch of a co-resident grid (static tile
-//     ownership, hand-off flags for trailing tiles, data-tagged 16-column strips for the panel chain);
-//     `chol_step_kernel` (one launch per block column, same body) is the fallback;
+//   * `chol_factor_persistent_kernel<false>`: the whole factorisation in ONE launch of a co-resident grid (static tile
+//     ownership, step-major scheduler, hand-off flags for trailing tiles, data-tagged 16-column strips for the panel
+//     chain); `chol_step_kernel` (one launch per block column, same body) is the fallback;
+//   * `chol_factor_persistent_kernel<true>`: the same body and hand-off rules under a per-tile scheduler, for a system
+//     that arrives in column chunks while the kernel is running (multi-GPU overlap);
 //   * `chol_backsolve_persistent_kernel`: the backward substitution in one launch, x itself is the hand-off flag.
 #include <hip/hip_runtime.h>
 #include <mutex>
@@ -33,41 +35,67 @@ namespace droid {
 
 constexpr int NB = CHOL_NB;
 
+// ---- diagnostics: all stamp storage, its exports and the stamp macros (nothing without the -D) --------------------
+// -DCHOL_STAMPS (tools/chol_stamps.py, tools/cfp_stamps.py), g_chol_stamps[(step & 31) * 32 + workgroup * 16 + slot]:
+//   TILE_STAMP   chol_tile, slots 0..10, first two panel workgroups of a step.  Per-step kernel (STEP_STAMP): s_memtime
+//                of thread 0 into the table.  Single-launch kernel (LDS_STAMP): wall clock (100 MHz, chip-wide) into LDS
+//                -- a global store would sit in front of the next s_waitcnt vmcnt(0) -- flushed at slot 8;
+//   GEMM_STAMP_* slots 9, 14, 15 (LDS): wave 0's first solve GEMM entered, operands loaded, MFMAs done;
+//   WAIT_STAMP   step-major scheduler, slots 11..13 = {wait begins, inputs seen, tile published};
+//   BS_STAMP     single-launch back-substitution, g_bs_stamps[workgroup * 8 + slot].
+// -DOV_DEBUG (tools/overlap_probe.py), g_ov_dbg: [63] = prologue done (either scheduler), [j] = diagonal tile j factored (<true>).
 #ifdef CHOL_STAMPS
-// Diagnostic build only.  Per-step kernel: s_memtime stamps of wave 0 of the first two panel workgroups.
-// Single-launch kernel: wall-clock (100 MHz, chip-wide) stamps of the diagonal workgroup and the one below it;
-// slots 11..13 = {wait begins, inputs seen, tile published}.
 __device__ unsigned long long g_chol_stamps[64 * 16];
-__shared__ unsigned long long g_chol_lstamps[16];  // slots 14, 15: inside wave 0's first solve GEMM (operands loaded, MFMAs done)
-#define STAMP(slot)                                                                         \
-  do {                                                                                      \
-    if (!PERSIST && threadIdx.x == 0 && panel && (blockIdx.x < 2)) {                                     \
-      g_chol_stamps[((k + 1) & 31) * 32 + blockIdx.x * 16 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    }                                                                                       \
-    if (PERSIST && threadIdx.x == 0 && panel && (bi - kp < 2)) {                              \
-      /* into LDS (a global store here would sit in front of the next s_waitcnt vmcnt(0)); flushed at slot 8 */ \
-      g_chol_lstamps[slot] = wall_clock64();                                                  \
-      if ((slot) == 2) { g_chol_lstamps[14] = 0; g_chol_lstamps[15] = 0; g_chol_lstamps[9] = 0; }                    \
-      if ((slot) == 8)                                                                        \
-        for (int ss = 0; ss < 16; ss++)                                                       \
-          if (ss < 11 || ss > 13) g_chol_stamps[((k + 1) & 31) * 32 + (bi - kp) * 16 + ss] = g_chol_lstamps[ss]; \
-    }                                                                                       \
-  } while (0)
-#define PSTAMP(slot)                                                                        \
-  do {                                                                                      \
-    if (t == 0 && panel && (bi - kp < 2)) g_chol_stamps[(kp & 31) * 32 + (bi - kp) * 16 + (slot)] = wall_clock64(); \
-  } while (0)
+__device__ unsigned long long g_bs_stamps[64 * 8];
+__shared__ unsigned long long g_chol_lstamps[16];
+extern "C" int droid_debug_chol_stamps(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chol_stamps), sizeof(unsigned long long) * 64 * 16);
+}
+extern "C" int droid_debug_bs_stamps(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_stamps), sizeof(unsigned long long) * 64 * 8);
+}
+#define STEP_STAMP(slot)                                                                                      \
+  do { if (threadIdx.x == 0 && panel && (blockIdx.x < 2))                                                      \
+    g_chol_stamps[((k + 1) & 31) * 32 + blockIdx.x * 16 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define LDS_STAMP(slot)                                                                                       \
+  do { if (threadIdx.x == 0 && panel && (bi - kp < 2)) {                                                       \
+    g_chol_lstamps[slot] = wall_clock64();                                                                    \
+    if ((slot) == 2) { g_chol_lstamps[14] = 0; g_chol_lstamps[15] = 0; g_chol_lstamps[9] = 0; }               \
+    if ((slot) == 8)                                                                                          \
+      for (int ss = 0; ss < 16; ss++)                                                                         \
+        if (ss < 11 || ss > 13) g_chol_stamps[((k + 1) & 31) * 32 + (bi - kp) * 16 + ss] = g_chol_lstamps[ss]; \
+  } } while (0)
+#define TILE_STAMP(slot) do { if (PERSIST) LDS_STAMP(slot); else STEP_STAMP(slot); } while (0)
+#define GEMM_STAMP_AT(slot) do { if (ASSIGN && threadIdx.x == 0 && g_chol_lstamps[slot] == 0) g_chol_lstamps[slot] = wall_clock64(); } while (0)
+#define GEMM_STAMP_ENTERED() GEMM_STAMP_AT(9)
+#define GEMM_STAMP_OPERANDS() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); GEMM_STAMP_AT(14); } while (0)
+#define GEMM_STAMP_DONE(acc) do { asm volatile("s_nop 15\n s_nop 15" : "+v"(acc)); GEMM_STAMP_AT(15); } while (0)
+#define WAIT_STAMP(slot) do { if (t == 0 && panel && (bi - kp < 2)) g_chol_stamps[(kp & 31) * 32 + (bi - kp) * 16 + (slot)] = wall_clock64(); } while (0)
+#define BS_STAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 64) g_bs_stamps[blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
 #else
-#define STAMP(slot) do { } while (0)
-#define PSTAMP(slot) do { } while (0)
+#define TILE_STAMP(slot) do { } while (0)
+#define GEMM_STAMP_ENTERED() do { } while (0)
+#define GEMM_STAMP_OPERANDS() do { } while (0)
+#define GEMM_STAMP_DONE(acc) do { } while (0)
+#define WAIT_STAMP(slot) do { } while (0)
+#define BS_STAMP(slot) do { } while (0)
+#endif
+#ifdef OV_DEBUG
+__device__ unsigned long long g_ov_dbg[64];
+extern "C" int droid_debug_overlap_stamps(unsigned long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ov_dbg), sizeof(unsigned long long) * 64);
+}
+#define OV_STAMP_ENTERED() do { if (blockIdx.x == 0 && threadIdx.x == 0) g_ov_dbg[63] = wall_clock64(); } while (0)
+#define OV_STAMP_DIAG(bi, bj, k) do { if (threadIdx.x == 0 && (bi) == (bj) && (bj) == (k) + 1 && (bj) < 62) g_ov_dbg[bj] = wall_clock64(); } while (0)
+#else
+#define OV_STAMP_ENTERED() do { } while (0)
+#define OV_STAMP_DIAG(bi, bj, k) do { } while (0)
 #endif
 constexpr int LDP = NB + 2;  // LDS row pitch in doubles: rows stay 16-B aligned, b64 MFMA operand reads conflict-free
 constexpr int WLP = 18;   // row pitch of an inverse block: with 16 the 16 rows of a GEMM operand read fell on two banks
 constexpr int WLB = 16 * WLP;  // doubles per inverse block
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 // LDS-qualified pointers: every helper below takes its tiles through these, so non-inlined helpers
 // read them with ds_read instead of flat loads and no generic-pointer casts are generated
@@ -206,19 +234,14 @@ __device__ __attribute__((noinline)) void wave_gemm_nt16(lds_f64* C, const lds_f
   const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
   f64x4 acc = {0.0, 0.0, 0.0, 0.0};
   double av[4], bv[4], cv[4];
-#ifdef CHOL_STAMPS
-  if (ASSIGN && threadIdx.x == 0 && g_chol_lstamps[9] == 0) g_chol_lstamps[9] = wall_clock64();   // function entered
-#endif
+  GEMM_STAMP_ENTERED();
 #pragma unroll
   for (int k = 0; k < 4; k++) { av[k] = lds_operand(&A[r * LDP + 4 * k + g]); bv[k] = lds_operand(&B[r * ldb + 4 * k + g]); }
   if (!ASSIGN) {  // the block to update travels with the operands instead of after the products
 #pragma unroll
     for (int i = 0; i < 4; i++) cv[i] = lds_operand(&C[(g + 4 * i) * LDP + r]);
   }
-#ifdef CHOL_STAMPS
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  if (ASSIGN && threadIdx.x == 0 && g_chol_lstamps[14] == 0) g_chol_lstamps[14] = wall_clock64();
-#endif
+  GEMM_STAMP_OPERANDS();
   {  // two chains of two instead of one of four: a dependent fp64 MFMA waits 18 cycles beyond the 64 of its predecessor
     f64x4 acc1 = {0.0, 0.0, 0.0, 0.0};
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0], bv[0], acc, 0, 0, 0);
@@ -227,10 +250,7 @@ __device__ __attribute__((noinline)) void wave_gemm_nt16(lds_f64* C, const lds_f
     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(av[3], bv[3], acc1, 0, 0, 0);
     acc += acc1;
   }
-#ifdef CHOL_STAMPS
-  asm volatile("s_nop 15\n s_nop 15" : "+v"(acc));
-  if (ASSIGN && threadIdx.x == 0 && g_chol_lstamps[15] == 0) g_chol_lstamps[15] = wall_clock64();
-#endif
+  GEMM_STAMP_DONE(acc);
 #pragma unroll
   for (int i = 0; i < 4; i++) C[(g + 4 * i) * LDP + r] = ASSIGN ? acc[i] : cv[i] - acc[i];
 }
@@ -310,7 +330,6 @@ __device__ __forceinline__ void wave_potrf16(lds_f64* Lb, lds_f64* Wl, const lds
   __builtin_amdgcn_s_setprio(0);
 }
 
-
 // 16-row strip of a 64x64 tile update: acc[0..NN) (row group rg, column tiles nt0..nt0+NN) -= Lr Lc^T.
 template <int NN>
 __device__ __forceinline__ void strip_update(f64x4 (&acc)[4], const lds_f64* Lr, const lds_f64* Lc, int rg,
@@ -384,29 +403,20 @@ __device__ __forceinline__ void block_update16(f64x4& acc, const lds_f64* A, con
   for (int k = 0; k < 4; k++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-av[k], bv[k], acc, 0, 0, 0);
 }
 
-// One step of the blocked right-looking factorisation in ONE launch of 512-thread workgroups:
-//   every tile (bi >= bj > k) of the trailing matrix:  A[bi,bj] -= L[bi,k] L[bj,k]^T
-//   tiles of block column k+1 additionally finish panel k+1: they rebuild and factor the updated
-//   diagonal tile A[k+1,k+1] (redundantly per workgroup: cheaper than a grid hand-off) and solve
-//   their own tile against it, so panel k+1 is ready when the launch ends.
-// k = -1 is the initial panel (no update).  Grid: (row blocks, column blocks) from k+1.
-//
-// Panel workgroups are organised around the pivot chain (wave 0), which is the critical path:
-//   * up front only the diagonal tile and column 0 of the tile to solve get the rank-64 update of
-//     the previous panel, spread as 16x16 tiles over the eight waves (wave 0: block (0,0) only,
-//     then straight into its factorisation; wave 4, which shares wave 0's SIMD, one tile);
-//   * per 16-column step p: {16x16 solves as GEMMs with the block inverse: one block per wave},
-//     then wave 0 updates block (p+1,p+1) and factors it while the other waves apply the
-//     remaining rank-16 updates of the diagonal tile and finish column p+1 of the tile to solve
-//     (its rank-64 update was deferred to this slot, where the matrix pipe is otherwise idle).
-// hand-off flags of the single-launch factorisation (agent scope = sc1: other XCDs see them)
+// ---- hand-off primitives of the single-launch factorisation; flags at agent scope = sc1: other XCDs see them ------
 constexpr int CFP_SPIN_LIMIT = 1 << 20;
-
-__device__ __forceinline__ int cfp_load(const int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+__device__ __forceinline__ int cfp_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void cfp_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// The one stall report (a bounded spin ran out).  Never hang: every workgroup sees `abort` before its next tile and
+// drains, the result is discarded.
+__device__ __forceinline__ void cfp_report_stall(int* fail, int* abortf) {
+  cfp_store(abortf, 1);
+  atomicMax(fail, 2);    // 2 = stalled grid (not a numerical failure): reported as STATUS_CHOL_STALL
 }
-__device__ __forceinline__ void cfp_store(int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// hand-over slot of the final panel tile L[row, col] (64x64, row pitch 64; layout of `ldiag`: ba_internal.hpp)
+__device__ __forceinline__ gbl_f64* lfin_slot(gbl_f64* Ldiag, int n, int row, int col) {
+  const int nrb = (n + 1 + NB - 1) / NB;  // block rows (row n = rhs)
+  return Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, row, col) * NB * NB;
 }
 
 // 16-column strip `sp` of a final panel tile -> LDS, by a 256-thread group, from the tile's hand-over slot
@@ -443,8 +453,7 @@ __device__ __forceinline__ void load_strip64(lds_f64* __restrict__ dst, const gb
     }
     if (there) break;
     if (++spins > CFP_SPIN_LIMIT || ((spins & 255) == 0 && cfp_load(abortf) == 1)) {
-      cfp_store(abortf, 1);  // never hang: the caller sees `abort` before its next tile, the result is discarded
-      atomicMax(fail, 2);    // 2 = stalled grid (not a numerical failure): reported as STATUS_CHOL_STALL
+      cfp_report_stall(fail, abortf);
       break;
     }
     __builtin_amdgcn_s_sleep(1);
@@ -468,9 +477,6 @@ __shared__ double g_cholBT[NB * LDP];
 __shared__ double g_cholWl[4 * WLB];
 __shared__ double g_cholIdn[WLB];  // (same padded pitch)
 
-// The body is shared by the one-launch-per-step kernel and the single-launch kernel below
-// (PERSIST: the workgroup is handed tile (bi, bj) of step k by its caller, the factored diagonal
-// tile goes to the side buffer Ldiag instead of overwriting the tile other workgroups still read).
 // Columns 16p..16p+15 of the solved tile (LDS, BT) are final: one wave writes them through and publishes the strip; the next
 // block column's workgroups start their rank-16 updates on it right away.  Scalar base + 32-bit lane offsets: with
 // per-lane 64-bit addresses and row predicates per store, ~200 loop-invariant instructions of this block were hoisted in
@@ -522,10 +528,27 @@ __device__ __forceinline__ void chol_strip_out(gbl_f64* __restrict__ S, int ld, 
   }
 }
 
-// coh_first (overlap mode, see chol_factor_persistent_kernel): the tile's own values were written by ANOTHER kernel
-// while this one was already running (no kernel-boundary invalidate in between), so this read of them must go past
-// the XCD's L2 (sc1); later reads see the workgroup's own write-through stores as before.
-// OV = false compiles the two overlap-mode parameters out (the default path pays nothing for them).
+// One step of the blocked right-looking factorisation in ONE launch of 512-thread workgroups:
+//   every tile (bi >= bj > k) of the trailing matrix:  A[bi,bj] -= L[bi,k] L[bj,k]^T
+//   tiles of block column k+1 additionally finish panel k+1: they rebuild and factor the updated diagonal tile
+//   A[k+1,k+1] (redundantly per workgroup: cheaper than a grid hand-off) and solve their own tile against it, so panel
+//   k+1 is ready when the launch ends.
+// k = -1 is the initial panel (no update).  Grid: (row blocks, column blocks) from k+1.
+// Panel workgroups are organised around the pivot chain (wave 0), which is the critical path:
+//   * up front only the diagonal tile and column 0 of the tile to solve get the rank-64 update of the previous panel,
+//     spread as 16x16 tiles over the eight waves (wave 0: block (0,0) only, then straight into its factorisation;
+//     wave 4, which shares wave 0's SIMD, one tile);
+//   * per 16-column step p: {16x16 solves as GEMMs with the block inverse: one block per wave}, then wave 0 updates
+//     block (p+1,p+1) and factors it while the other waves apply the remaining rank-16 updates of the diagonal tile
+//     and finish column p+1 of the tile to solve (its rank-64 update was deferred to this slot, where the matrix pipe
+//     is otherwise idle).
+// The body is shared by the one-launch-per-step kernel and the single-launch kernels below (PERSIST: the workgroup is
+// handed tile (bi, bj) of step k by its scheduler, the factored diagonal tile goes to the side buffer Ldiag instead of
+// overwriting the tile other workgroups still read).  OV (overlap scheduler only; compiled out otherwise):
+//   coh_first: the tile's own values were written by ANOTHER kernel while this one was already running (no
+//     kernel-boundary invalidate in between), so this read of them must go past the XCD's L2 (sc1); later reads see
+//     the workgroup's own write-through stores as before;
+//   k_last > k: a plain trailing tile replays the updates of the block columns k..k_last in one go.
 template <bool PERSIST, bool OV = false>
 __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld, int k, int bi, int bj,
                                           int* __restrict__ fail, double lm, double ep,
@@ -565,15 +588,13 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
       }
       return;
     }
-    const int p0 = k * NB;
     frag_load_global<2>(acc, S, ld, r0, q0, w4, 2 * grp, nrows, n, bi == bj, coh_first);
     if (PERSIST && bj == kp + 1) {
       // tiles of the NEXT panel column take the two panel tiles strip by strip out of the hand-over slots, like
       // the panel workgroups do: their update ends right behind the last strip instead of a flag, an
       // acknowledgement and two whole-tile loads later, so the next step's panel workgroups find their tile ready
-      const int nrb = (nrows + NB - 1) / NB;
-      const gbl_f64* slot0 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, bi, k) * NB * NB;
-      const gbl_f64* slot1 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, bj, k) * NB * NB;
+      const gbl_f64* slot0 = lfin_slot(Ldiag, n, bi, k);
+      const gbl_f64* slot1 = lfin_slot(Ldiag, n, bj, k);
       const lds_f64* Bx = (bi == bj) ? B0 : B1;
       for (int sp = 0; sp < 4; sp++) {
         if (grp == 0) load_strip64(B0, slot0, r0, sp, r0, nrows, fail, abortf);
@@ -613,7 +634,7 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
   // diagonal tile (only the rhs row, and only when the last block column is narrower than NB)
   const bool solve_rows = !diag || (wk < NB);
   if (t < 256) Idn[(t >> 4) * WLP + (t & 15)] = ((t >> 4) == (t & 15)) ? 1.0 : 0.0;  // visible after the barrier below
-  STAMP(0);
+  TILE_STAMP(0);
   // 16x16 tiles (rg, nt): D = diagonal tile (lower part), T = the tile to solve.  Only what the
   // first pivot block and the first solve need is updated up front (all of D, column 0 of T);
   // columns 1..3 of T stay in registers and are finished one per 16-column step, left-looking,
@@ -664,14 +685,13 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
     // The two panel tiles arrive in 16-column strips (their producers write a strip into the tile's data-tagged
     // hand-over slot as soon as it is solved): strips 0..2 and their rank-16 updates overlap with the producers'
     // remaining work, only the last strip's load and update stay in front of the first pivot block.
-    const int nrb = (nrows + NB - 1) / NB;
-    const gbl_f64* slot1 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, kp, k) * NB * NB;  // L[kp,k]
-    const gbl_f64* slot0 = Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, bi, k) * NB * NB;  // L[bi,k]
+    const gbl_f64* slot1 = lfin_slot(Ldiag, n, kp, k);  // L[kp,k]
+    const gbl_f64* slot0 = lfin_slot(Ldiag, n, bi, k);  // L[bi,k]
     for (int sp = 0; sp < 4; sp++) {
       if (grp == 0) load_strip64(B1, slot1, c0, sp, c0, n, fail, abortf);
       else load_strip64(B0, slot0, r0, sp, r0, nrows, fail, abortf);
       __syncthreads();
-      if (sp == 3) STAMP(1);
+      if (sp == 3) TILE_STAMP(1);
       if (sp == 3 && wave == 0) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
       for (int i = 0; i < 2; i++) {
@@ -696,7 +716,7 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
     }
   } else {
     __syncthreads();
-    STAMP(1);
+    TILE_STAMP(1);
   }
   auto store_solve = [&](const f64x4& a, int rg, int nt) {
 #pragma unroll
@@ -731,12 +751,12 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
       }
     }
   }
-  STAMP(2);
+  TILE_STAMP(2);
   // block (0,0) was updated and written by wave 0 alone: factor it right away
   if (wave == 0) wave_potrf16(&B2[0], &Wl[0], Idn, fail, diag);
-  STAMP(3);
+  TILE_STAMP(3);
   __syncthreads();
-  STAMP(4);
+  TILE_STAMP(4);
 
 #pragma unroll 1  // one copy of the step body: iterations 1..3 then run from a warm instruction cache
   for (int p = 0; p < 4; p++) {
@@ -750,19 +770,19 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
         wave_gemm_nt16<true>(&BT[(16 * g) * LDP + 16 * p], &BT[(16 * g) * LDP + 16 * p], &Wl[WLB * p], WLP);
       }
     }
-    if (p == 0) STAMP(10);
+    if (p == 0) TILE_STAMP(10);
     __syncthreads();
-    if (p == 0) STAMP(5);
+    if (p == 0) TILE_STAMP(5);
     if (PERSIST && solve_rows && wave == 4)
-      chol_strip_out(S, ld, Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index((nrows + NB - 1) / NB, bi, kp) * NB * NB, BT,
-                     r0, c0, wk, nrows, p, (p == 3) ? &done[bi] : nullptr, 4 * kp + 3);
+      chol_strip_out(S, ld, lfin_slot(Ldiag, n, bi, kp), BT, r0, c0, wk, nrows, p, (p == 3) ? &done[bi] : nullptr,
+                     4 * kp + 3);
     if (p == 3) break;
     const int q = p + 1;
     if (wave == 0) {  // the pivot chain: next diagonal block, then its factorisation
       wave_gemm_nt16<false>(&B2[(16 * q) * LDP + 16 * q], &B2[(16 * q) * LDP + 16 * p],
                             &B2[(16 * q) * LDP + 16 * p], LDP);
       wave_potrf16(&B2[(16 * q) * LDP + 16 * q], &Wl[WLB * q], Idn, fail, diag);
-      if (p == 0) STAMP(6);
+      if (p == 0) TILE_STAMP(6);
     } else {
       // the other rank-16 updates of the diagonal tile, round-robin over the less loaded waves (not wave 4: it
       // shares the pivot wave's SIMD and writes the strips out)
@@ -796,9 +816,9 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
       }
     }
     __syncthreads();
-    if (p == 0) STAMP(7);
+    if (p == 0) TILE_STAMP(7);
   }
-  STAMP(8);
+  TILE_STAMP(8);
   if (PERSIST && bi == kp + 1 && kp + 1 < (n + NB - 1) / NB) {
     // The tile right below the diagonal also leaves M = X L_kk^-1 (X = the solved tile L[kp+1,kp]) for the
     // back-substitution, which then multiplies by M^T instead of solving with L_kk^T on its critical chain:
@@ -859,7 +879,7 @@ __device__ __forceinline__ void chol_tile(gbl_f64* __restrict__ S, int n, int ld
   } else if (solve_rows && !PERSIST) {  // (single launch: the strips went out one by one)
     store_tile64(S, BT, ld, r0, c0, max(r0, c0 + wk), min(r0 + NB, nrows), wk, false);
   }
-  if (!PERSIST) STAMP(9);
+  if (!PERSIST) TILE_STAMP(9);
 }
 
 __global__ __launch_bounds__(512) void chol_step_kernel(double* __restrict__ S, int n, int ld, int k,
@@ -868,29 +888,34 @@ __global__ __launch_bounds__(512) void chol_step_kernel(double* __restrict__ S, 
                    nullptr, nullptr);
 }
 
-// ---------------------------------------------------------------------------------------------
-// The whole factorisation in ONE launch.  A kernel boundary per block column costs 3-4.5 us of
-// the 17 us step and makes the pivot chain wait for the slowest trailing tile; here a grid of
-// co-resident workgroups (one per CU: 145 KB of LDS) walks the steps itself.
-//   * static ownership: lower-triangle tiles in column-major order, tile idx -> workgroup
-//     idx % grid; a workgroup applies every step to its own tiles, so a tile's intermediate
-//     versions never change hands (and panel tiles come first in every workgroup's step);
-//   * data flow instead of barriers: done[i] = 4*c + 3 once the final tile L[i, c] of block row i is completely
-//     in the matrix, dver[j] = trailing updates applied to the diagonal tile (j, j) by its owner (0 = damped).
-//     A trailing tile (bi, bj) at step k waits for done[bi], done[bj] >= 4k+3; a panel tile waits for
-//     dver[k+1] >= k and then takes the two panel tiles strip by strip out of their data-tagged hand-over slots,
-//     as they are written; so do the trailing tiles of the next panel column (no flag at all);
-//     nothing waits for unrelated trailing tiles (look-ahead comes for free);
-//   * hand-off without cache maintenance: every tile store is written through (sc1), tiles of other
-//     workgroups are read with sc1 loads, the flags likewise: store, s_waitcnt vmcnt(0), barrier, flag |
-//     flag poll, barrier, loads.  Rows are 128-byte aligned (ld % 16 == 0) so tiles of different
-//     workgroups never share a cache line of the per-XCD L2s;
-//   * the factored diagonal tile L_jj goes to Ldiag[j] (64x64): the other panel workgroups of the
-//     column read the unfactored tile at their own pace;
-//   * every spin is bounded: a stalled grid raises `abort`, reports a failed factorisation and
-//     drains (it cannot happen with a resident grid; the GPU is never left hanging).
+// ---- the whole factorisation in ONE launch ----------------------------------------------------------------------
+// A kernel boundary per block column costs 3-4.5 us of the 17 us step and makes the pivot chain wait for the slowest
+// trailing tile; here a grid of co-resident workgroups (one per CU: 145 KB of LDS) schedules the tiles itself.
+//   * static ownership: lower-triangle tiles in column-major order, tile idx -> workgroup idx % grid; a workgroup
+//     applies every step to its own tiles, so a tile's intermediate versions never change hands;
+//   * data flow instead of barriers: done[i] = 4*c + 3 once the final tile L[i, c] of block row i is completely in the
+//     matrix, dver[j] = trailing updates applied to the diagonal tile (j, j) by its owner (0 = damped).  What a tile
+//     needs before a step: cfp_input; nothing waits for unrelated trailing tiles (look-ahead comes for free);
+//   * hand-off without cache maintenance: every tile store is written through (sc1), tiles of other workgroups are
+//     read with sc1 loads, the flags likewise: store, s_waitcnt vmcnt(0), barrier, flag | flag poll, barrier, loads.
+//     Rows are 128-byte aligned (ld % 16 == 0) so tiles of different workgroups never share a line of the XCDs' L2s;
+//   * the factored diagonal tile L_jj goes to Ldiag[j] (64x64): the other panel workgroups of the column read the
+//     unfactored tile at their own pace;
+//   * every spin is bounded: a stalled grid raises `abort`, reports a failed factorisation and drains (it cannot
+//     happen with a resident grid; the GPU is never left hanging).
+// WHEN a workgroup runs which of its tiles is the scheduler's business, and chol_factor_persistent_kernel<OV> is one of
+// two, as explicit specialisations of the one template:
+//   <false>, the product path, step-major: for every step k the workgroup walks its tiles of the trailing matrix in
+//            ownership order (panel tiles first) and WAITS for each tile's inputs;
+//   <true>,  multi-GPU overlap, per tile: every owned tile keeps its own next step; the workgroup polls the inputs
+//            once, runs the first tile that can go and skips the others.
+// The rules both obey are stated once: the inputs of a step (cfp_input), the publication of the damped diagonal tiles
+// and of their later versions, the stall report, the slot address (lfin_slot).  What differs stays in each scheduler:
+// waiting versus polling once, spin limits and sleeps, the k_last replay.  The four-line column advance (tile index ->
+// (bi, bj)) and the tile-count loop of <false> are written out on purpose: as a helper, as chol_tiles(n), they change
+// the code of <false> (profiles/chol_refactor_isa.txt).
 
-// One tile of one step.  NOT inlined into the step loops: inlined, the loop-invariant lane offsets of the
+// One tile of one step.  NOT inlined into the schedulers' loops: inlined, the loop-invariant lane offsets of the
 // whole body are hoisted in front of the loops and held (or spilled) across them.
 template <bool OV>
 __device__ __attribute__((noinline)) void chol_tile_persist(double* __restrict__ S, int n, int ld, int k, int bi,
@@ -900,164 +925,74 @@ __device__ __attribute__((noinline)) void chol_tile_persist(double* __restrict__
   chol_tile<true, OV>((gbl_f64*)S, n, ld, k, bi, bj, fail, lm, ep, (gbl_f64*)Ldiag, done, abortf, coh_first, k_last);
 }
 
-// OVERLAP mode (ready != nullptr; multi-GPU, SURVEY 8e / VERDICT r02 #6): the kernel is launched BEFORE the reduced
-// system is there.  The all-reduce of the packed system (block-column major) runs in column chunks on a side stream;
-// each chunk is expanded into S (damping applied there: pass lm = ep = 0 here) and then ready[block column] = epoch
-// is published for its block columns.  A tile (bi, bj) is first read by its owner at its first step: that read waits
-// for ready[bj] and goes past the L2 (sc1); a plain trailing tile then replays all the updates it has missed in one
-// go (chol_tile, k_last).  Why columns: row i of L needs every earlier column, so a late block ROW costs a sweep as
-// long as the factorisation itself (measured: profiles/r03_overlap_emulation.txt), while a late block COLUMN j is not
-// needed before the chain gets there, ~10.8 us x j after the start.
-// The grid is capped below the CU count by the launcher, so the collective's and the unpack kernels always find CUs.
-#ifdef OV_DEBUG
-__device__ unsigned long long g_ov_dbg[64];
-extern "C" int droid_debug_overlap_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ov_dbg), sizeof(unsigned long long) * 64);
-}
-#endif
+// The input rule.  What lane `lane` of wave 0 must see before tile (bi, bj) takes step k (k = -1: the initial panel;
+// `panel`: bj == k + 1): a flag word that has reached `need`, or a hand-over slot whose first value no longer carries
+// the preset tag; neither = nothing.
+//   lanes 0, 1  plain trailing tile (bj > k + 2): both panel tiles L[bi,k], L[bj,k] are completely in the matrix,
+//               done[] >= 4k + 3.  Panel tiles and tiles of the next panel column (bj = k + 2) take them strip by
+//               strip out of the hand-over slots inside the body instead (no flag at all);
+//   lane 2      panel tile below the diagonal: its column's diagonal tile carries all k updates, dver[bj] >= k;
+//   lane 3      OV, the tile's first step: its block column has been reduced, ready[bj] >= epoch;
+//   lanes 4, 5  OV, the tiles that wait for strips inside the body: the producers of L[bi,k], L[bj,k] have started
+//               writing (a producer in a late block row would otherwise park the workgroup, its other tiles with it).
+struct CfpInput { const int* flag; int need; const gbl_f64* slot; };
+__device__ __forceinline__ bool cfp_waits_for_done(int bj, int k, bool panel) { return k >= 0 && !panel && bj != k + 2; }
+__device__ __forceinline__ int cfp_first_step(int bj) { return (bj == 0) ? -1 : 0; }  // column 0 has the initial panel step only
 template <bool OV>
-__global__ __launch_bounds__(512) void chol_factor_persistent_kernel(double* __restrict__ S, int n, int ld,
-                                                                     int* __restrict__ fail, double lm, double ep,
-                                                                     int* __restrict__ flags,
-                                                                     double* __restrict__ Ldiag,
-                                                                     const int* __restrict__ ready_arg, int epoch) {
-  const int* const ready = OV ? ready_arg : nullptr;   // (OV = false: every overlap branch below is compiled out)
+__device__ __forceinline__ CfpInput cfp_input(int lane, int bi, int bj, int k, bool panel, const int* done,
+                                              const int* dver, const int* ready, int epoch, double* Ldiag, int n) {
+  const bool flagged = cfp_waits_for_done(bj, k, panel);
+  CfpInput in = {nullptr, 4 * k + 3, nullptr};
+  if (lane == 0 && flagged) in.flag = &done[bi];
+  else if (lane == 1 && flagged && bj != bi) in.flag = &done[bj];
+  else if (lane == 2 && k >= 0 && panel && bi != bj) { in.flag = &dver[bj]; in.need = k; }
+  else if (OV && lane == 3 && k == cfp_first_step(bj)) { in.flag = &ready[bj]; in.need = epoch; }
+  else if (OV && (lane == 4 || lane == 5) && k >= 0 && (panel || bj == k + 2))
+    in.slot = lfin_slot((gbl_f64*)Ldiag, n, lane == 4 ? bi : bj, k);
+  return in;
+}
+
+// The owner of a diagonal tile publishes its version -- 0: damped (prologue), v: v trailing updates applied (not after
+// its panel step: there the strips are the publication) -- once every wave's write-through stores are acknowledged.
+__device__ __forceinline__ void cfp_publish_diag(int* dver, int bj, int version) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) cfp_store(&dver[bj], version);
+}
+
+template <bool OV>
+__global__ __launch_bounds__(512) void chol_factor_persistent_kernel(
+    double* __restrict__ S, int n, int ld, int* __restrict__ fail, double lm, double ep, int* __restrict__ flags,
+    double* __restrict__ Ldiag, const int* __restrict__ ready, int epoch);
+
+// The step-major scheduler.  Every input is WAITED for, CFP_SPIN_LIMIT rounds of s_sleep(1): the system is in memory
+// when the kernel starts and a producer is a few tiles away at most.  (`ready`, `epoch`: unused; null and 0.)
+template <>
+__global__ __launch_bounds__(512) void chol_factor_persistent_kernel<false>(
+    double* __restrict__ S, int n, int ld, int* __restrict__ fail, double lm, double ep, int* __restrict__ flags,
+    double* __restrict__ Ldiag, const int* __restrict__, int) {
   __shared__ int s_abort;
   const int nb = (n + NB - 1) / NB;       // block columns
   const int nrb = (n + 1 + NB - 1) / NB;  // block rows (row n = rhs)
-  int* done = flags;
-  int* dver = flags + nrb;
-  int* abortf = flags + 2 * nrb;
+  int *done = flags, *dver = flags + nrb, *abortf = flags + 2 * nrb;
   const int G = (int)gridDim.x, wg = (int)blockIdx.x, t = (int)threadIdx.x;
-  int total = 0;
+  int total = 0;  // = chol_tiles(n), as the loop it has always been (see above)
   for (int j = 0; j < nb; j++) total += nrb - j;
-
-  {  // damping diag += ep + lm*diag (dk:1197) of the blocks >= 1 by the owners of their diagonal tiles
-    int cs = 0;
+  {  // prologue: damping diag += ep + lm*diag (dk:1197) of the blocks >= 1 by the owners of their diagonal tiles
+    int cs = 0;  // index of tile (j, j)
     for (int j = 0; j < nb; j++) {
       if (j >= 1 && (cs % G) == wg) {
         const int i = j * NB + t;
-        if (ready == nullptr && t < NB && i < n) {   // (overlap mode: the rows are not there yet; damped by the unpack)
+        if (t < NB && i < n) {
           const double d = S[(size_t)i * ld + i];
           gstore<true>((gbl_f64*)&S[(size_t)i * ld + i], d + (ep + lm * d));
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the write-through stores have been acknowledged
-        __syncthreads();
-        if (t == 0) cfp_store(&dver[j], 0);
+        cfp_publish_diag(dver, j, 0);
       }
       cs += nrb - j;
     }
   }
-
-#ifdef OV_DEBUG
-  if (blockIdx.x == 0 && threadIdx.x == 0) g_ov_dbg[63] = wall_clock64();
-#endif
-  if (OV && ready != nullptr) {
-    // ---- overlap mode: per-tile progress instead of the step-major walk below.  A workgroup owns up to a handful of
-    // tiles; stepping them in lockstep would park it at step 0 on a tile whose block column arrives with the LAST chunk
-    // of the collective while its other tile sits on the chain.  Here every owned tile keeps its own next step; wave 0
-    // scans them in ownership order (earlier block columns first), takes the first whose inputs are there -- the same
-    // flags as below, polled once instead of waited for, plus ready[bi] at the tile's first step -- and spins
-    // (bounded) only when none is.  Dependencies only point to earlier block columns, so skipping a waiting tile can
-    // never starve the tile that is picked.
-    constexpr int MAXT = 12;   // the launcher admits at most 10 tiles per workgroup
-    __shared__ int s_ti[MAXT], s_tj[MAXT], s_nx[MAXT], s_nt, s_pick, s_klast;
-    if (t == 0) {
-      int nt = 0, cj = 0, cs = 0;
-      for (int idx = wg; idx < total && nt < MAXT; idx += G) {
-        while (idx >= cs + (nrb - cj)) {
-          cs += nrb - cj;
-          cj++;
-        }
-        s_ti[nt] = cj + (idx - cs);
-        s_tj[nt] = cj;
-        s_nx[nt] = (cj == 0) ? -1 : 0;     // column 0 has the initial panel step only
-        nt++;
-      }
-      s_nt = nt;
-    }
-    __syncthreads();
-    while (true) {
-      if (t < 64) {
-        int pick = -1, spins = 0, klast = -2;
-        bool ok = true;
-        const int nt = s_nt;
-        while (true) {
-          bool any_left = false;
-          for (int i = 0; i < nt; i++) {
-            const int bi = s_ti[i], bj = s_tj[i], k = s_nx[i];
-            if (k > bj - 1) continue;      // this tile is final (last step: its panel step k = bj - 1)
-            any_left = true;
-            const int kp = k + 1;
-            const bool panel = (bj == kp);
-            const bool first = (k == ((bj == 0) ? -1 : 0));
-            const int* p = nullptr;
-            int need = 4 * k + 3;
-            const bool flagged = k >= 0 && !panel && bj != kp + 1;
-            if (t == 0 && flagged) p = &done[bi];
-            else if (t == 1 && flagged && bj != bi) p = &done[bj];
-            else if (t == 2 && k >= 0 && panel && bi != bj) { p = &dver[bj]; need = k; }
-            else if (t == 3 && first) p = &ready[bj], need = epoch;    // the tile's block column has been reduced
-            const int fv = (p == nullptr) ? 0x7fffffff : cfp_load(p);
-            bool sat = fv >= need;
-            // Panel tiles and tiles of the next panel column take their two panel tiles strip by strip out of the
-            // hand-over slots INSIDE the body, and wait there: enter only once the producers have started writing
-            // (first strip of each slot no longer carries the preset tag) -- a producer in a block row that comes
-            // with a late chunk would otherwise park this workgroup, and its other tiles with it.
-            if ((t == 4 || t == 5) && k >= 0 && (panel || bj == kp + 1)) {
-              const int r = (t == 4) ? bi : (panel ? kp : bj);
-              const gbl_f64* sl = (const gbl_f64*)Ldiag + chol_lfin_offset(n) + (size_t)chol_tile_index(nrb, r, k) * NB * NB;
-              sat = __double_as_longlong(gload<true>(sl)) != CFP_TAG;
-            }
-            if (__all(sat)) {
-              pick = i;
-              klast = k;
-              if (flagged) {  // plain trailing tile: how far are BOTH rows final?  done = 4 c + 3 for the last final column c
-                const int d0 = __shfl(fv, 0), d1 = (bj != bi) ? __shfl(fv, 1) : d0;
-                const int cok = (min(d0, d1) - 3) >> 2;
-                klast = max(k, min(cok, bj - 3));   // k = bj - 2 takes the strips from the slots, k = bj - 1 is the panel step
-              }
-              break;
-            }
-          }
-          if (!any_left) pick = -2;
-          if (pick != -1) break;
-          if (++spins > (CFP_SPIN_LIMIT << 2) || ((spins & 63) == 0 && __any(cfp_load(abortf) == 1))) {
-            ok = false;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(4);
-        }
-        if (t == 0) {
-          s_pick = ok ? pick : -3;
-          s_klast = klast;
-          if (!ok) {
-            cfp_store(abortf, 1);
-            atomicMax(fail, 2);
-          }
-        }
-      }
-      __syncthreads();  // also: the previous tile's LDS reads are over
-      const int pick = s_pick;
-      if (pick < 0) return;   // -2: every owned tile is final; -3: stalled (reported)
-      const int bi = __builtin_amdgcn_readfirstlane(s_ti[pick]), bj = __builtin_amdgcn_readfirstlane(s_tj[pick]);
-      const int k = __builtin_amdgcn_readfirstlane(s_nx[pick]);
-      const bool first = (k == ((bj == 0) ? -1 : 0));
-      const int klast = __builtin_amdgcn_readfirstlane(s_klast);
-      chol_tile_persist<true>(S, n, ld, k, bi, bj, fail, lm, ep, Ldiag, done, abortf, first, klast);
-#ifdef OV_DEBUG
-      if (t == 0 && bi == bj && bj == k + 1 && bj < 62) g_ov_dbg[bj] = wall_clock64();   // diagonal tile of column bj factored
-#endif
-      if (bj != k + 1 && bi == bj) {  // publish the next version of a diagonal tile
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t == 0) cfp_store(&dver[bj], max(k, klast) + 1);
-      }
-      __syncthreads();
-      if (t == 0) s_nx[pick] = max(k, klast) + 1;
-      __syncthreads();
-    }
-  }
+  OV_STAMP_ENTERED();
 
   int colstart = 0;  // index of tile (kp, kp)
 #pragma unroll 1
@@ -1074,59 +1009,144 @@ __global__ __launch_bounds__(512) void chol_factor_persistent_kernel(double* __r
       const int bj = __builtin_amdgcn_readfirstlane(cj), bi = __builtin_amdgcn_readfirstlane(cj + (idx - cs));
       if (k < 0 && bj != 0) break;  // step -1 is the first panel only
       const bool panel = (bj == kp);
-      // ---- wait for the inputs (wave 0: one flag per lane)
-      PSTAMP(11);
-      const bool first_touch = (ready != nullptr) && (k <= 0);   // step -1: column 0; step 0: every other tile
-      if (t < 64) {
+      WAIT_STAMP(11);
+      if (t < 64) {  // wave 0: one input per lane
         bool ok = true;
-        if (k >= 0 || first_touch) {
-          // plain tile: both panel tiles complete (all four strips); panel tile: only the diagonal tile's
-          // version here, the strips are awaited inside the body
-          const int* p = nullptr;
-          int need = 4 * k + 3;
-          const bool flagged = k >= 0 && !panel && bj != kp + 1;  // tiles of the next panel column poll the hand-over slots
-          if (t == 0 && flagged) p = &done[bi];
-          else if (t == 1 && flagged && bj != bi) p = &done[bj];
-          else if (t == 2 && k >= 0 && panel && bi != bj) { p = &dver[bj]; need = k; }
-          else if (t == 3 && first_touch) { p = &ready[bj]; need = epoch; }   // the tile's block column has been reduced
-          bool sat = (p == nullptr);
+        if (k >= 0) {
+          const CfpInput in = cfp_input<false>(t, bi, bj, k, panel, done, dver, nullptr, 0, Ldiag, n);
+          bool sat = (in.flag == nullptr);
           int spins = 0;
-          // overlap mode waits for the collective (and, when ranks share a GPU, for another rank's grid): seconds, not ms
-          const int limit = (ready != nullptr) ? (CFP_SPIN_LIMIT << 4) : CFP_SPIN_LIMIT;
           while (true) {
-            if (!sat) sat = cfp_load(p) >= need;
+            if (!sat) sat = cfp_load(in.flag) >= in.need;
             if (__all(sat)) break;
             spins++;
-            if (spins > limit || ((spins & 255) == 0 && __any(cfp_load(abortf) == 1))) {
+            if (spins > CFP_SPIN_LIMIT || ((spins & 255) == 0 && __any(cfp_load(abortf) == 1))) {
               ok = false;
               break;
             }
-            if (ready != nullptr) __builtin_amdgcn_s_sleep(4);
-            else __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_s_sleep(1);
           }
         } else if (__any(cfp_load(abortf) == 1)) {
           ok = false;
         }
         if (t == 0) {
           s_abort = ok ? 0 : 1;
-          if (!ok) {
-            cfp_store(abortf, 1);
-            atomicMax(fail, 2);
-          }
+          if (!ok) cfp_report_stall(fail, abortf);
         }
       }
-      PSTAMP(12);
+      WAIT_STAMP(12);
       __syncthreads();  // also: the previous tile's LDS reads are over
       if (s_abort) return;
       chol_tile_persist<false>(S, n, ld, k, bi, bj, fail, lm, ep, Ldiag, done, abortf, false, k);
-      if (!panel && bi == bj) {  // publish the next version of a diagonal tile (panel tiles publish their strips)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave's write-through stores are acknowledged
-        __syncthreads();
-        if (t == 0) cfp_store(&dver[bj], k + 1);
-      }
-      PSTAMP(13);
+      if (!panel && bi == bj) cfp_publish_diag(dver, bj, k + 1);
+      WAIT_STAMP(13);
     }
     colstart += nrb - kp;
+  }
+}
+
+// The per-tile scheduler of OVERLAP mode (multi-GPU, SURVEY 8e / VERDICT r02 #6): the kernel is launched BEFORE the
+// reduced system is there.  The all-reduce of the packed system (block-column major) runs in column chunks on a side
+// stream; each chunk is expanded into S (damped there: lm = ep = 0 here) and then ready[block column] = epoch is
+// published for its block columns.  A tile's first read of its own values needs ready[bj] and goes past the L2
+// (`coh_first`); a plain trailing tile then replays all the updates it has missed in one go (`k_last`).  Why columns:
+// row i of L needs every earlier column, so a late block ROW costs a sweep as long as the factorisation itself
+// (profiles/r03_overlap_emulation.txt), while a late block COLUMN j is not needed before the chain gets there, ~10.8 us
+// x j after the start.  The launcher caps the grid below the CU count: the collective and the unpack kernels find CUs.
+// Why per tile: a workgroup owns up to a handful of tiles; stepping them in lockstep would park it at step 0 on a tile
+// whose block column arrives with the LAST chunk while its other tile sits on the chain.  Wave 0 scans the owned tiles
+// in ownership order (earlier block columns first), takes the first whose inputs are all there -- polled once -- and
+// spins only when none is: s_sleep(4) and 4 x CFP_SPIN_LIMIT rounds, because this wait is for the collective (and,
+// when ranks share a GPU, for another rank's grid): seconds, not ms.  Dependencies only point to earlier block
+// columns, so skipping a waiting tile can never starve the tile that is picked.
+// Precondition: `ready` is not null (lane 3 of cfp_input reads it); launch_chol_factor_overlap is the only launcher.
+template <>
+__global__ __launch_bounds__(512) void chol_factor_persistent_kernel<true>(
+    double* __restrict__ S, int n, int ld, int* __restrict__ fail, double lm, double ep, int* __restrict__ flags,
+    double* __restrict__ Ldiag, const int* __restrict__ ready, int epoch) {
+  constexpr int MAXT = 12;   // the launcher admits at most 10 tiles per workgroup
+  __shared__ int s_ti[MAXT], s_tj[MAXT], s_nx[MAXT], s_nt, s_pick, s_klast;
+  const int nb = (n + NB - 1) / NB;       // block columns
+  const int nrb = (n + 1 + NB - 1) / NB;  // block rows (row n = rhs)
+  int *done = flags, *dver = flags + nrb, *abortf = flags + 2 * nrb;
+  const int G = (int)gridDim.x, wg = (int)blockIdx.x, t = (int)threadIdx.x;
+  const int total = (int)chol_tiles(n);
+  {  // prologue: the rows are not there yet and arrive damped by the unpack kernel; only the versions are published
+    int cs = 0;  // index of tile (j, j)
+    for (int j = 0; j < nb; j++) {
+      if (j >= 1 && (cs % G) == wg) cfp_publish_diag(dver, j, 0);
+      cs += nrb - j;
+    }
+  }
+  OV_STAMP_ENTERED();
+  if (t == 0) {  // the owned tiles, each with its first step
+    int nt = 0, cj = 0, cs = 0;
+    for (int idx = wg; idx < total && nt < MAXT; idx += G) {
+      while (idx >= cs + (nrb - cj)) {
+        cs += nrb - cj;
+        cj++;
+      }
+      s_ti[nt] = cj + (idx - cs);
+      s_tj[nt] = cj;
+      s_nx[nt] = cfp_first_step(cj);
+      nt++;
+    }
+    s_nt = nt;
+  }
+  __syncthreads();
+  while (true) {
+    if (t < 64) {  // wave 0: one input per lane
+      int pick = -1, spins = 0, klast = -2;
+      bool ok = true;
+      const int nt = s_nt;
+      while (true) {
+        bool any_left = false;
+        for (int i = 0; i < nt; i++) {
+          const int bi = s_ti[i], bj = s_tj[i], k = s_nx[i];
+          if (k > bj - 1) continue;      // this tile is final (last step: its panel step k = bj - 1)
+          any_left = true;
+          const bool panel = (bj == k + 1);
+          const CfpInput in = cfp_input<true>(t, bi, bj, k, panel, done, dver, ready, epoch, Ldiag, n);
+          const int fv = (in.flag == nullptr) ? 0x7fffffff : cfp_load(in.flag);
+          const bool sat = (in.slot != nullptr) ? __double_as_longlong(gload<true>(in.slot)) != CFP_TAG : fv >= in.need;
+          if (__all(sat)) {
+            pick = i;
+            klast = k;
+            if (cfp_waits_for_done(bj, k, panel)) {
+              // plain trailing tile: how far are BOTH rows final?  done = 4 c + 3 for the last final column c (lanes 0, 1)
+              const int d0 = __shfl(fv, 0), d1 = (bj != bi) ? __shfl(fv, 1) : d0;
+              const int cok = (min(d0, d1) - 3) >> 2;
+              klast = max(k, min(cok, bj - 3));   // k = bj - 2 takes the strips from the slots, k = bj - 1 is the panel step
+            }
+            break;
+          }
+        }
+        if (!any_left) pick = -2;
+        if (pick != -1) break;
+        if (++spins > (CFP_SPIN_LIMIT << 2) || ((spins & 63) == 0 && __any(cfp_load(abortf) == 1))) {
+          ok = false;
+          break;
+        }
+        __builtin_amdgcn_s_sleep(4);
+      }
+      if (t == 0) {
+        s_pick = ok ? pick : -3;
+        s_klast = klast;
+        if (!ok) cfp_report_stall(fail, abortf);
+      }
+    }
+    __syncthreads();  // also: the previous tile's LDS reads are over
+    const int pick = s_pick;
+    if (pick < 0) return;   // -2: every owned tile is final; -3: stalled (reported)
+    const int bi = __builtin_amdgcn_readfirstlane(s_ti[pick]), bj = __builtin_amdgcn_readfirstlane(s_tj[pick]);
+    const int k = __builtin_amdgcn_readfirstlane(s_nx[pick]);
+    const int klast = __builtin_amdgcn_readfirstlane(s_klast);   // > k: the body replays the steps k..klast in one go
+    chol_tile_persist<true>(S, n, ld, k, bi, bj, fail, lm, ep, Ldiag, done, abortf, k == cfp_first_step(bj), klast);
+    OV_STAMP_DIAG(bi, bj, k);
+    if (bj != k + 1 && bi == bj) cfp_publish_diag(dver, bj, max(k, klast) + 1);
+    __syncthreads();
+    if (t == 0) s_nx[pick] = max(k, klast) + 1;
+    __syncthreads();
   }
 }
 
@@ -1184,12 +1204,6 @@ __global__ __launch_bounds__(256) void chol_backsolve_kernel(double* __restrict_
 // separate flag, fence or drain is needed; MI355X guide: data-tagged 8-byte granules).  The grid
 // is co-resident (<= BSP_MAX_BLOCKS workgroups, one per CU) and every spin is bounded.
 constexpr int BSP_MAX_BLOCKS = 200;
-#ifdef CHOL_STAMPS
-__device__ unsigned long long g_bs_stamps[64 * 8];
-#define BSTAMP(slot) do { if (threadIdx.x == 0 && blockIdx.x < 64) g_bs_stamps[blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
-#else
-#define BSTAMP(slot) do { } while (0)
-#endif
 constexpr long long BSP_SENTINEL = -1LL;
 
 // 64x64 tile -> LDS by the 192 threads of waves 1..3 (11 independent 16-byte loads per thread)
@@ -1231,7 +1245,7 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
   const int j = blockIdx.x;
   const int c0 = j * NB;
   const int wj = min(NB, n - c0);
-  BSTAMP(0);
+  BS_STAMP(0);
   if (t == 0) dead = 0;
   if (FAST) load_tile64(DROID_LDS(Ld), (const gbl_f64*)Ldiag + (size_t)j * NB * NB, NB, 0, 0, 0, wj, wj, true, 1.0);
   else load_tile64(DROID_LDS(Ld), (const gbl_f64*)S, ld, c0, c0, c0, c0 + wj, c0 + wj, true, 1.0);
@@ -1278,7 +1292,7 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
         __builtin_amdgcn_s_sleep(1);
       }
     }
-    if (k == j + 1) BSTAMP(1);
+    if (k == j + 1) BS_STAMP(1);
     xk[t] = xv;  // same wave writes and reads: LDS operations of one wave are ordered
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
@@ -1308,13 +1322,13 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
     }
     cur ^= 1;
     if (!FAST && k == j + 1) {
-      BSTAMP(2);
+      BS_STAMP(2);
       break;  // nothing left to prefetch: wave 0 goes straight into the diagonal solve
     }
     __syncthreads();  // tile k-1 landed, tile k consumed
     if (dead) return;
   }
-  BSTAMP(3);
+  BS_STAMP(3);
   if (t < 64) {
     // L_jj^T x = z by one wave, lane t = unknown t.  Measured: the plain 64-step lane-broadcast
     // loop cost 150 cycles per step (an LDS read of L[i][t] inside every dependent step).  Here
@@ -1376,22 +1390,22 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
 #undef DROID_BS_BLOCK
 #undef DROID_BS_WTERM
 #undef DROID_BS_STEP
-    BSTAMP(2);
+    BS_STAMP(2);
     if (FAST && j < nb - 1) xsol -= poll_matvec(j + 1, Mc);  // x_j = L_jj^-T z' - M^T x_{j+1}
     if (__double_as_longlong(xsol) == BSP_SENTINEL) xsol = __longlong_as_double(0x7ff8000000000000LL);
-    BSTAMP(4);
+    BS_STAMP(4);
     if (t < wj) __hip_atomic_store(&x[c0 + t], xsol, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    BSTAMP(5);
+    BS_STAMP(5);
   }
 }
 
 // ---- host side: the launchers of a CholSystem (ba_internal.hpp) ------------------------------------------------
-// launch_chol_factor: the single-launch kernel where chol_single_launch allows it, else one chol_step_kernel per block
-// column.  launch_chol_backsolve: the persistent kernel for 2 .. BSP_MAX_BLOCKS block columns (FAST after a
-// single-launch factorisation: it reads L_jj from `ldiag`), else one chol_backsolve_kernel per block column, which
-// reads L_jj from the matrix: after a single-launch factorisation chol_ldiag_to_sys_kernel first copies them back.
-
-// Diagnostic and test switches of the solver, read once per process.
+// launch_chol_factor: the step-major single-launch kernel where chol_single_launch allows it, else one chol_step_kernel
+// per block column.  launch_chol_factor_overlap: the per-tile single-launch kernel or nothing.  launch_chol_backsolve:
+// the persistent kernel for 2 .. BSP_MAX_BLOCKS block columns (FAST after a single-launch factorisation: it reads
+// L_jj from `ldiag`), else one chol_backsolve_kernel per block column, which reads L_jj from the matrix: after a
+// single-launch factorisation chol_ldiag_to_sys_kernel first copies them back.  Spinning grids: launch_spinning_grid.
+// Diagnostic and test switches of the solver; every variable is read once per process.
 struct CholSwitches {
   bool multi_launch;       // DROID_CHOL_MULTI_LAUNCH: the per-step kernels only
   bool cooperative;        // DROID_CHOL_COOPERATIVE=1: persistent grids through hipLaunchCooperativeKernel (see below)
@@ -1400,47 +1414,19 @@ struct CholSwitches {
   int overlap_reserve;     // DROID_OVERLAP_RESERVE_CUS (default 32): CUs the overlap factorisation leaves free
 };
 static const CholSwitches& chol_switches() {
-  static const CholSwitches sw = {
-      getenv("DROID_CHOL_MULTI_LAUNCH") != nullptr,
-      getenv("DROID_CHOL_COOPERATIVE") != nullptr && atoi(getenv("DROID_CHOL_COOPERATIVE")) != 0,
-      getenv("DROID_CHOL_FORCE_BS_REFUSAL") != nullptr,
-      getenv("DROID_CHOL_GRID") ? atoi(getenv("DROID_CHOL_GRID")) : 0,
-      getenv("DROID_OVERLAP_RESERVE_CUS") ? atoi(getenv("DROID_OVERLAP_RESERVE_CUS")) : 32};
+  const auto is_set = [](const char* name) { return getenv(name) != nullptr; };
+  const auto number = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+  static const CholSwitches sw = {is_set("DROID_CHOL_MULTI_LAUNCH"), number("DROID_CHOL_COOPERATIVE", 0) != 0,
+                                  is_set("DROID_CHOL_FORCE_BS_REFUSAL"), number("DROID_CHOL_GRID", 0),
+                                  number("DROID_OVERLAP_RESERVE_CUS", 32)};
   return sw;
 }
-
-// Single-launch path: needs 128-byte aligned rows (no cache line shared between tiles of different workgroups) and a
-// grid that is resident as a whole.
-static int chol_resident_workgroups() {
-  static int cached = -1;
-  if (cached < 0) {
-    int dev = 0, occ = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, chol_factor_persistent_kernel<false>, 512, 0) != hipSuccess)
-      cached = 0;
-    else
-      cached = occ * prop.multiProcessorCount;
-  }
-  return cached;
-}
-
-static bool chol_single_launch(const CholSystem& c) {
-  const int nb = (c.n + NB - 1) / NB;
-  // beyond ~10 tiles per resident workgroup (n ~ 4400 on 256 CUs) the trailing updates, serialised inside the
-  // persistent workgroups, outweigh the saved kernel boundaries (measured cross-over: n = 4500)
-  return !chol_switches().multi_launch && nb >= 2 && (c.ld % 16) == 0 && (reinterpret_cast<uintptr_t>(c.S) % 128) == 0 &&
-         chol_resident_workgroups() >= 8 && chol_tiles(c.n) <= (size_t)10 * chol_resident_workgroups();
-}
-
-// grid of a single-launch factorisation: one workgroup per tile, `cap` at most
-static int chol_factor_grid(int n, int cap) { return chol_tiles(n) < (size_t)cap ? (int)chol_tiles(n) : cap; }
 
 // ---- residency of the single-launch kernels ------------------------------------------------------------------
 // Both persistent kernels spin across workgroups, so their whole grid must be resident.  A plain launch gives that
 // whenever nothing else holds the CUs for good: ordinary kernels of other streams only delay the dispatch of the
 // remaining workgroups.  The one thing that can deadlock is ANOTHER spinning grid:
-//   * within a process (two streams / threads calling `ba`): serialised here.  When a persistent launch arrives on
+//   * within a process (two streams / threads calling `ba`): serialised.  When a persistent launch arrives on
 //     a different stream than the previous one, an event recorded on the previous stream is waited for first, so
 //     two such grids never overlap.  Single-stream use (the SLAM loop) never records or waits.
 //   * across processes sharing one GPU: DROID_CHOL_COOPERATIVE=1 launches through hipLaunchCooperativeKernel,
@@ -1448,30 +1434,68 @@ static int chol_factor_grid(int n, int cap) { return chol_tiles(n) < (size_t)cap
 //     tools/micro/coop_launch.hip, which is why it is not the default); if the launch is refused the per-step
 //     kernels run instead.  A stall that happens anyway ends in the bounded spins: fail flag = 2, reported as
 //     STATUS_CHOL_STALL (an error, unlike the numerical STATUS_CHOL_FAIL whose dx = 0 is the reference's behaviour).
-struct PersistState {
+struct PersistState {   // per device
   hipStream_t last = nullptr;
   hipEvent_t ev = nullptr;
   bool any = false;
+  int resident = -1;   // workgroups of the factorisation that fit the device at once; -1: not asked yet
 };
 static PersistState g_persist[64];
 static std::mutex g_persist_mu;
 
-// Returns the lock: the caller keeps it until its spinning grid is ENQUEUED, so that another host thread cannot record
-// its "previous stream" event in front of this launch (with the lock released before the launch, thread B
-// could order itself behind thread A's stream before A's grid was in it, and the two grids could overlap).
-static std::unique_lock<std::mutex> persist_enter(hipStream_t s) {
-  std::unique_lock<std::mutex> lock(g_persist_mu);
+// Workgroups of the factorisation kernel (145 KB of LDS: one per CU) that are resident together on the current
+// device; 0 when that cannot be found out, or for a device outside the table.
+static int chol_resident_workgroups() {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return lock;
-  PersistState& st = g_persist[dev];
-  if (st.any && st.last != s) {
-    if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) st.ev = nullptr;
-    if (st.ev && hipEventRecord(st.ev, st.last) == hipSuccess) (void)hipStreamWaitEvent(s, st.ev, 0);
-    (void)hipGetLastError();  // a destroyed previous stream must not poison this call
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  std::lock_guard<std::mutex> lock(g_persist_mu);
+  int& cached = g_persist[dev].resident;
+  if (cached < 0) {
+    int occ = 0;
+    hipDeviceProp_t prop;
+    const bool known = hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, chol_factor_persistent_kernel<false>, 512, 0) == hipSuccess;
+    cached = known ? occ * prop.multiProcessorCount : 0;
   }
-  st.last = s;
-  st.any = true;
-  return lock;
+  return cached;
+}
+
+// Single-launch path: needs 128-byte aligned rows (no cache line shared between tiles of different workgroups) and a
+// grid that is resident as a whole.  Returns the resident workgroups (asked once per launch), 0: not this way.
+static int chol_single_launch(const CholSystem& c) {
+  const int nb = (c.n + NB - 1) / NB;
+  if (chol_switches().multi_launch || nb < 2 || (c.ld % 16) != 0 || (reinterpret_cast<uintptr_t>(c.S) % 128) != 0) return 0;
+  // beyond ~10 tiles per resident workgroup (n ~ 4400 on 256 CUs) the trailing updates, serialised inside the
+  // persistent workgroups, outweigh the saved kernel boundaries (measured cross-over: n = 4500)
+  const int resident = chol_resident_workgroups();
+  return (resident >= 8 && chol_tiles(c.n) <= (size_t)10 * resident) ? resident : 0;
+}
+
+// The one way a spinning grid is enqueued: behind the previous one of this device, then plainly or -- with
+// DROID_CHOL_COOPERATIVE -- cooperatively.  false: not launched, the cooperative launch was refused (the grid cannot
+// be resident now) or counts as refused (`refuse`: DROID_CHOL_FORCE_BS_REFUSAL); the caller falls back.
+// The lock is kept until the grid is ENQUEUED, so that another host thread cannot record its "previous stream" event
+// in front of this launch (with the lock released before the launch, thread B could order itself behind
+// thread A's stream before A's grid was in it, and the two grids could overlap).
+static bool launch_spinning_grid(const void* fn, int workgroups, int threads, void** args, hipStream_t s, bool refuse = false) {
+  std::lock_guard<std::mutex> lock(g_persist_mu);
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
+    PersistState& st = g_persist[dev];
+    if (st.any && st.last != s) {
+      if (!st.ev && hipEventCreateWithFlags(&st.ev, hipEventDisableTiming) != hipSuccess) st.ev = nullptr;
+      if (st.ev && hipEventRecord(st.ev, st.last) == hipSuccess) (void)hipStreamWaitEvent(s, st.ev, 0);
+      (void)hipGetLastError();  // a destroyed previous stream must not poison this call
+    }
+    st.last = s, st.any = true;
+  }
+  if (!chol_switches().cooperative) {
+    (void)hipLaunchKernel(fn, dim3(workgroups), dim3(threads), args, 0, s);
+    return true;
+  }
+  if (!refuse && hipLaunchCooperativeKernel(fn, dim3(workgroups), dim3(threads), args, 0, s) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
 }
 
 // The single-launch factorisation leaves the factored diagonal tiles L_jj in the side buffer `ldiag`, not in the
@@ -1486,40 +1510,30 @@ __global__ __launch_bounds__(256) void chol_ldiag_to_sys_kernel(double* __restri
   }
 }
 
-// Overlap mode: the single-launch kernel only (false when it cannot be used: the caller then unpacks the whole system
-// and solves the ordinary way).  `ready` [block columns] / `epoch`: see the kernel.  The grid leaves
-// `overlap_reserve` CUs free for the collective and the unpack kernels.
+// A single-launch factorisation, either scheduler: one workgroup per tile, `cap` at most.  false: not launched.
+static bool launch_factor_grid(const void* fn, CholSystem c, double lm, double ep, const int* ready, int epoch, int cap,
+                               hipStream_t s) {
+  void* args[] = {&c.S, &c.n, &c.ld, &c.fail, &lm, &ep, &c.flags, &c.ldiag, &ready, &epoch};
+  return launch_spinning_grid(fn, chol_tiles(c.n) < (size_t)cap ? (int)chol_tiles(c.n) : cap, 512, args, s);
+}
+
+// Overlap mode: the per-tile single-launch kernel only (false when it cannot be used: the caller then unpacks the whole
+// system and solves the ordinary way).  `ready` [block columns] / `epoch`: see the kernel; the unpack kernel damps, so
+// lm = ep = 0 here.  The grid leaves `overlap_reserve` CUs free for the collective and the unpack kernels.
 bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s) {
   const CholSwitches& sw = chol_switches();
-  if (c.n <= 0 || !ready || sw.cooperative || !chol_single_launch(c)) return false;
-  const int cap = chol_resident_workgroups() - (sw.overlap_reserve > 0 ? sw.overlap_reserve : 0);
+  if (c.n <= 0 || !ready || sw.cooperative) return false;
+  const int cap = chol_single_launch(c) - (sw.overlap_reserve > 0 ? sw.overlap_reserve : 0);
   if (cap < 8 || chol_tiles(c.n) > (size_t)10 * cap) return false;
-  auto lock = persist_enter(s);
-  const double zero = 0.0;
-  hipLaunchKernelGGL(chol_factor_persistent_kernel<true>, dim3(chol_factor_grid(c.n, cap)), dim3(512), 0, s, c.S, c.n,
-                     c.ld, c.fail, zero, zero, c.flags, c.ldiag, ready, epoch);
-  return true;
+  return launch_factor_grid((const void*)chol_factor_persistent_kernel<true>, c, 0.0, 0.0, ready, epoch, cap, s);
 }
 
 bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s) {
   if (c.n <= 0) return false;
-  const CholSwitches& sw = chol_switches();
-  if (chol_single_launch(c)) {
-    int cap = chol_resident_workgroups();
-    if (sw.grid >= 8 && sw.grid < cap) cap = sw.grid;
-    const dim3 grid(chol_factor_grid(c.n, cap));
-    CholSystem a = c;
-    const int* no_ready = nullptr;
-    int no_epoch = 0;
-    void* args[] = {&a.S, &a.n, &a.ld, &a.fail, &lm, &ep, &a.flags, &a.ldiag, &no_ready, &no_epoch};
-    const void* fn = (const void*)chol_factor_persistent_kernel<false>;
-    auto lock = persist_enter(s);
-    if (!sw.cooperative) {
-      (void)hipLaunchKernel(fn, grid, dim3(512), args, 0, s);
-      return true;
-    }
-    if (hipLaunchCooperativeKernel(fn, grid, dim3(512), args, 0, s) == hipSuccess) return true;
-    (void)hipGetLastError();  // refused (grid cannot be resident now): per-step kernels below
+  if (int cap = chol_single_launch(c)) {
+    const int grid = chol_switches().grid;
+    if (grid >= 8 && grid < cap) cap = grid;
+    if (launch_factor_grid((const void*)chol_factor_persistent_kernel<false>, c, lm, ep, nullptr, 0, cap, s)) return true;
   }
   const int nb = (c.n + NB - 1) / NB;        // block columns
   const int nrb = (c.n + 1 + NB - 1) / NB;   // block rows (row n = rhs)
@@ -1532,19 +1546,13 @@ bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s
 void launch_chol_backsolve(const CholSystem& c, bool factor_single, hipStream_t s) {
   const int nb = (c.n + NB - 1) / NB;
   if (nb >= 2 && nb <= BSP_MAX_BLOCKS) {
-    const CholSwitches& sw = chol_switches();
     CholSystem a = c;
     const double* ld_arg = factor_single ? c.ldiag : nullptr;
     void* args[] = {&a.S, &a.n, &a.ld, &a.x, &a.fail, &ld_arg};
     const void* fn = factor_single ? (const void*)chol_backsolve_persistent_kernel<true>
                                    : (const void*)chol_backsolve_persistent_kernel<false>;
-    auto lock = persist_enter(s);
-    if (!sw.cooperative) {
-      (void)hipLaunchKernel(fn, dim3(nb), dim3(256), args, 0, s);
-      return;
-    }
-    if (!sw.force_bs_refusal && hipLaunchCooperativeKernel(fn, dim3(nb), dim3(256), args, 0, s) == hipSuccess) return;
-    (void)hipGetLastError();  // refused: the per-step kernels below (`x` carries the sentinel preset, they overwrite all of it)
+    // refused: the per-step kernels below (`x` carries the sentinel preset, they overwrite all of it)
+    if (launch_spinning_grid(fn, nb, 256, args, s, chol_switches().force_bs_refusal)) return;
   }
   if (factor_single)
     hipLaunchKernelGGL(chol_ldiag_to_sys_kernel, dim3(nb), dim3(256), 0, s, c.S, c.n, c.ld, c.ldiag);
@@ -1589,15 +1597,6 @@ CholSystem::CholSystem(double* scratch, int n_, double* x_, int* fail_)
   ldiag = S + (size_t)(n + 1) * ld;
   flags = reinterpret_cast<int*>(ldiag + chol_ldiag_doubles(n));
 }
-
-#ifdef CHOL_STAMPS
-extern "C" int droid_debug_bs_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bs_stamps), sizeof(unsigned long long) * 64 * 8);
-}
-extern "C" int droid_debug_chol_stamps(unsigned long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chol_stamps), sizeof(unsigned long long) * 64 * 16);
-}
-#endif
 
 // helper for droid_chol_solve: pack (A, b) into the augmented layout
 __global__ void chol_pack_kernel(const double* __restrict__ A, const double* __restrict__ b,

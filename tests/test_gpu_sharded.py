@@ -230,3 +230,101 @@ def test_overlap_chunks_feed_a_running_factorisation(backends, oracle):
     from util import ba_args
     ref = oracle.ba(*ba_args(prob), iters, prob.lm, prob.ep, False, storage_f32=True)
     assert np.abs(pb - ref["poses"]).max() < 1e-4 and np.abs(db_ - ref["disps"]).max() < 1e-4
+
+
+_CAPPED_CHILD = r"""
+import sys, numpy as np, torch
+sys.path[:0] = [r"%(root)s", r"%(root)s/droid-slam_reserch_amd"]
+from droid_backends import ba_driver, synth
+world, iters = 2, 2
+prob = synth.make_ba_problem(N=64, E=2000, H=48, W=64, seed=3, lm=1e-5, ep=1e-2)
+ranges = ba_driver.partition_frames(prob.ii, prob.t1, world)
+dev = torch.device("cuda", 0)
+t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+def run(overlap):
+    shards = [ba_driver.shard_problem(prob, ranges, r) for r in range(world)]
+    probs = [ba_driver.BAProblemDev(poses=t(prob.poses), disps=t(prob.disps), intrinsics=t(prob.intrinsics),
+                                    disps_sens=t(prob.disps_sens), targets=t(sh["targets"]), weights=t(sh["weights"]),
+                                    eta=t(sh["eta"]), ii=t(sh["ii"]), jj=t(sh["jj"])) for sh in shards]
+    bes = [ba_driver.HipBackend() for _ in range(world)]
+    for r in range(world):
+        bes[r].prepare(probs[r], prob.t0, prob.t1, shards[r]["own"], False)
+    side, main = torch.cuda.Stream(), torch.cuda.current_stream()
+    started = []
+    for it in range(iters):
+        total = None
+        for r in range(world):
+            packed = bes[r].build_packed(probs[r], False)
+            total = packed.clone() if total is None else total + packed
+        for r in range(world):
+            if not overlap:
+                bes[r].packed.copy_(total)
+                bes[r].unpack(False)
+                bes[r].solve_update(probs[r], prob.lm, prob.ep, False)
+                continue
+            plan = bes[r].overlap_plan()
+            assert len(plan) >= 3 and plan[0][0] == 0 and plan[-1][1] == total.numel()
+            ready = torch.cuda.Event()
+            ready.record(main)
+            started.append(bool(bes[r].solve_update_overlap(probs[r], it + 1, False)))   # spins on the device from here on
+            if not started[-1]:                         # refused: this rank spins on nothing and nothing may be fed to it
+                torch.cuda.synchronize()                # (what an earlier rank or iteration started has been fed in full)
+                return None, None, started, []
+            with torch.cuda.stream(side):
+                side.wait_event(ready)
+                for c, (a, b) in enumerate(plan):
+                    torch.cuda._sleep(200000)                                  # ~0.1 ms between chunks
+                    bes[r].packed[a:b].copy_(total[a:b])
+                    bes[r].unpack_chunk(c, prob.lm, prob.ep, it + 1)
+            main.wait_stream(side)
+    torch.cuda.synchronize()
+    status = [int(bes[r].status()[0]) for r in range(world)]
+    disps = np.array(prob.disps, copy=True)
+    for r in range(world):
+        f0, f1 = ranges[r]
+        disps[f0:f1] = probs[r].disps[f0:f1].cpu().numpy()
+    same = all(torch.equal(probs[r].poses, probs[0].poses) for r in range(1, world))
+    return probs[0].poses.cpu().numpy(), disps, started, status + [int(same)]
+
+pa, da, _, sa = run(False)
+pb, db, started, sb = run(True)
+if pb is None:
+    pb, db = np.zeros_like(pa), np.zeros_like(da)
+np.savez(r"%(out)s", pa=pa, da=da, pb=pb, db=db, started=np.array(started), sa=np.array(sa), sb=np.array(sb))
+"""
+
+
+def test_overlap_scheduler_scans_several_owned_tiles(tmp_path, backends, oracle):
+    """test_overlap_chunks_feed_a_running_factorisation gives every workgroup of the overlap factorisation ONE tile (27
+    tiles on 200+ workgroups), so the per-tile scheduler never has a tile to skip.  Here the grid is capped at 8
+    workgroups -- DROID_OVERLAP_RESERVE_CUS = CU count - 8; the switch is read once per process, hence the child --
+    for the same 64-keyframe graph: 6 block columns, 27 tiles, 3-4 tiles per workgroup, replay depth up to 2.  Two
+    shards, chunks delivered with the same pauses.  The overlap must have been taken (a refusal must not pass
+    silently), no status bit, and the same bars as the one-tile case: the ordinary sequence to 1e-6 / 1e-5, the oracle
+    to 1e-4."""
+    import subprocess
+    import torch
+    from droid_backends import synth
+    from util import ba_args
+    assert torch.cuda.is_available()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert cus > 8
+    e = dict(os.environ)
+    e["DROID_OVERLAP_RESERVE_CUS"] = str(cus - 8)
+    out_file = os.path.join(str(tmp_path), "capped.npz")
+    out = subprocess.run([sys.executable, "-c", _CAPPED_CHILD % {"root": ROOT, "out": out_file}], env=e,
+                         capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr[-2000:]
+    o = np.load(out_file)
+    assert len(o["started"]) > 0 and o["started"].all(), "the capped overlap factorisation was refused"
+    assert len(o["started"]) == 4                                   # 2 shards x 2 iterations
+    for st in (o["sa"], o["sb"]):
+        assert all(int(x) & 15 == 0 for x in st[:-1]) and int(st[-1]) == 1, st    # status words; replicas bit-identical
+    pa, da, pb, db_ = o["pa"], o["da"], o["pb"], o["db"]
+    print(f"capped overlap vs ordinary sequence: poses {np.abs(pa - pb).max():.3e} disps {np.abs(da - db_).max():.3e}")
+    assert np.abs(pa - pb).max() < 1e-6 and np.abs(da - db_).max() < 1e-5
+    prob = synth.make_ba_problem(N=64, E=2000, H=48, W=64, seed=3, lm=1e-5, ep=1e-2)
+    ref = oracle.ba(*ba_args(prob), 2, prob.lm, prob.ep, False, storage_f32=True)
+    print(f"capped overlap vs oracle: poses {np.abs(pb - ref['poses']).max():.3e} disps {np.abs(db_ - ref['disps']).max():.3e}")
+    assert np.abs(pb - ref["poses"]).max() < 1e-4 and np.abs(db_ - ref["disps"]).max() < 1e-4
