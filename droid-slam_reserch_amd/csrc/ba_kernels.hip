@@ -811,7 +811,8 @@ constexpr int SF_PITCH = SF_TP + 4;   // 16-byte aligned rows, conflict-free 16-
 constexpr int SF_MAXT = 11;           // max 16x16 output tiles per wave: ceil(7*6/4)
 
 // E row (6 values) of one (edge, pixel); T = the edge's relative pose (R row-major, t)
-__device__ __forceinline__ void e_row(const Intr& K, const float* T, bool stereo, float X0, float X1, float disp,
+template <typename S>
+__device__ __forceinline__ void e_row(const Intr& K, const S* T, bool stereo, S X0, S X1, float disp,
                                       float wu_raw, float wv_raw, float* eij) {
   const PixLin L = jacobians_pixel(K, T, T + 9, X0, X1, disp);
   float wu = L.valid * (0.001f * wu_raw), wv = L.valid * (0.001f * wv_raw);
@@ -1091,7 +1092,7 @@ constexpr int S2_MAXT = 6;                 // 6 row tiles of 16 at 16 edges: 21 
 struct Schur2Meta {
   int e[S2_MAXE];
   int flag[S2_MAXE];
-  float T[S2_MAXE][12];
+  double T[S2_MAXE][12];   // fp64: the staged rows are formed from the point the linearisation formed A from
 };
 
 // One workgroup = 4 waves that alternate between staging (VALU) and the SYRK (matrix pipe); three workgroups per
@@ -1141,7 +1142,7 @@ __global__ __launch_bounds__(256, 3) void ba_schur2_kernel(BaView v, const float
   if (tid < nedges) {
     const int e = v.seg_edge[x_beg + tid];
     const int jx = (int)jj[e];
-    const RelMat<float> T = rel_pose_mat<float, true>(poses, f, jx);
+    const RelMat<double> T = rel_pose_mat<double, true>(poses, f, jx);
     sm.e[tid] = e;
     sm.flag[tid] = (jx == f) ? 1 : 0;
 #pragma unroll
@@ -1195,6 +1196,7 @@ __global__ __launch_bounds__(256, 3) void ba_schur2_kernel(BaView v, const float
   }
 
   prefetch(tile_beg);
+  const double inv_fx = 1.0 / (double)K.fx, inv_fy = 1.0 / (double)K.fy;   // one division per thread, not two per tile
   for (int tile = tile_beg; tile < tile_end; tile++) {
     const int k = tile * SF_TP + pixl;
     const bool pok = k < HW;
@@ -1204,21 +1206,21 @@ __global__ __launch_bounds__(256, 3) void ba_schur2_kernel(BaView v, const float
     for (int u = 0; u < 2 * NU; u++) cur_w[u] = pf_w[u];
     if (tile > tile_beg) __syncthreads();  // the previous tile has been multiplied
     // ---- stage B~ = E sqrt(Q) of 64 pixels
-    const float X0 = ((float)(k % W) - K.cx) / K.fx, X1 = ((float)(k / W) - K.cy) / K.fy;
+    const double X0 = ((double)(k % W) - (double)K.cx) * inv_fx, X1 = ((double)(k / W) - (double)K.cy) * inv_fy;
 #pragma unroll
     for (int u = 0; u < NU; u++) {
       const int x = part + 4 * u;
       if (x < nedges) {
         float eij[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (pok && sm.flag[x] == 0) {  // stereo pairs carry no weight in the pose terms (dk:323, :356): zero rows
-          const float* T = sm.T[x];
-          const float px = T[0] * X0 + T[1] * X1 + T[2] + disp * T[9];
-          const float py = T[3] * X0 + T[4] * X1 + T[5] + disp * T[10];
-          const float pz = T[6] * X0 + T[7] * X1 + T[8] + disp * T[11];
-          const bool bad = pz < DROID_MIN_DEPTH;
-          const float d = bad ? 0.f : 1.0f / pz;
+          const double* T = sm.T[x];
+          const double px = T[0] * X0 + T[1] * X1 + T[2] + (double)disp * T[9];
+          const double py = T[3] * X0 + T[4] * X1 + T[5] + (double)disp * T[10];
+          const double pz = T[6] * X0 + T[7] * X1 + T[8] + (double)disp * T[11];
+          const bool bad = pz < (double)DROID_MIN_DEPTH;
+          const float d = bad ? 0.f : recip_f(pz);
           PixLin L;
-          pix_jacobians(K, px, py, d, disp, T[9], T[10], T[11], L);
+          pix_jacobians(K, (float)px, (float)py, d, disp, (float)T[9], (float)T[10], (float)T[11], L);
           const float val = bad ? 0.f : 0.001f * sq;   // weights are scaled by 0.001 (dk:305-306), rows by sqrt(Q)
           const float su = (val * cur_w[2 * u]) * L.Jzu, sv = (val * cur_w[2 * u + 1]) * L.Jzv;
 #pragma unroll
@@ -1851,7 +1853,7 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
     const float* __restrict__ intrinsics, const float* __restrict__ weights,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const double* __restrict__ xsol,
     float* __restrict__ dz_out) {
-  __shared__ SlotMeta sm;
+  __shared__ SlotMetaT<double> sm;     // fp64 relative poses: the E rows come from the point of the linearisation
   __shared__ float dxs[SLOT_MAXE][6];  // dx of each edge's target pose (0 when it does not feed back)
   if ((int)blockIdx.x >= min(v.hdr[HDR_M], v.M)) return;
   const int m = v.order[blockIdx.x];
@@ -1859,16 +1861,17 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
   const int f = v.kx[m];
   const Intr K = {intrinsics[0], intrinsics[1], intrinsics[2], intrinsics[3]};
   int kpix[BSUB_PPT];
-  float disp[BSUB_PPT], acc[BSUB_PPT];
-  float bx0[BSUB_PPT], bx1[BSUB_PPT];  // back-projected pixel, once per pixel
+  float disp[BSUB_PPT];
+  double acc[BSUB_PPT];
+  double bx0[BSUB_PPT], bx1[BSUB_PPT];  // back-projected pixel, once per pixel
 #pragma unroll
   for (int p = 0; p < BSUB_PPT; p++) {
     kpix[p] = (blockIdx.y * BSUB_PPT + p) * 256 + threadIdx.x;
     disp[p] = kpix[p] < HW ? disps[(size_t)f * HW + kpix[p]] : 0.f;
-    acc[p] = 0.f;
+    acc[p] = 0.0;
     const int kk = kpix[p] < HW ? kpix[p] : 0;
-    bx0[p] = ((float)(kk % v.W) - K.cx) / K.fx;
-    bx1[p] = ((float)(kk / v.W) - K.cy) / K.fy;
+    bx0[p] = ((double)(kk % v.W) - (double)K.cx) / (double)K.fx;
+    bx1[p] = ((double)(kk / v.W) - (double)K.cy) / (double)K.fy;
   }
   const int pf = f - v.t0;
   // the self row exists for frames of the owned window (entry 0 of the slot) and feeds back
@@ -1894,7 +1897,7 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
       float c[6];
       for (int n = 0; n < 6; n++) c[n] = (on && !failed) ? (float)xsol[6 * pj + n] : 0.f;
       if (self_on) {
-        const float* T = sm.T[threadIdx.x];
+        const double* T = sm.T[threadIdx.x];
         for (int k = 0; k < 6; k++) {  // (Adj d)_k = (Adj^T e_k) . d
           float ek[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, col[6];
           ek[k] = 1.f;
@@ -1932,16 +1935,16 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
       fetch_w(x + 1);
       const bool edge_on = sm.ent[x] != 0;
       if (!(edge_on || self_on)) continue;
-      float T[12];
+      double T[12];
 #pragma unroll
       for (int n = 0; n < 12; n++) T[n] = sm.T[x][n];
 #pragma unroll
       for (int p = 0; p < BSUB_PPT; p++) {
         float eij[6];
         e_row(K, T, sm.flag[x] != 0, bx0[p], bx1[p], disp[p], wraw[p][0], wraw[p][1], eij);
-        float dw = 0.f;
+        double dw = 0.0;
 #pragma unroll
-        for (int n = 0; n < 6; n++) dw += eij[n] * dxs[x][n];
+        for (int n = 0; n < 6; n++) dw += (double)eij[n] * (double)dxs[x][n];
         acc[p] += dw;
       }
     }
@@ -1950,7 +1953,7 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
   for (int p = 0; p < BSUB_PPT; p++) {
     if (kpix[p] >= HW) continue;
     const size_t o = (size_t)m * HW + kpix[p];
-    const float dz = v.Q[o] * (v.w[o] - acc[p]);
+    const float dz = (float)((double)v.Q[o] * ((double)v.w[o] - acc[p]));
     if (dz_out) dz_out[o] = dz;
     disps[(size_t)f * HW + kpix[p]] = disp[p] + dz;
   }

@@ -198,21 +198,31 @@ __device__ __forceinline__ PixLin linearize_pixel(const Intr& K, const Rel& T, f
   return L;
 }
 
-// Jacobians only (E rows of the Schur complement and of the back-substitution), fp32 matrix form:
-// 12 FMAs for the transform.  ru / rv are not set.
+// Jacobians only (E rows of the Schur complement and of the back-substitution), matrix form: 12 FMAs for the
+// transform.  ru / rv are not set.  S = the type the point is transformed in.  S = double gives the Jacobians the
+// point of linearize_pixel_d: H = A - S cancels by a factor of 30..70 where a few close points dominate both (scenes
+// of tests/hard_scenes.py), and a rounding of the point that A does not share is amplified by that factor.
 // X0, X1: the back-projected pixel ((u - cx) / fx, (v - cy) / fy), formed once per pixel by the caller
-__device__ __forceinline__ PixLin jacobians_pixel(const Intr& K, const float* R, const float* t, float X0, float X1,
-                                                  float disp) {
-  const float x = R[0] * X0 + R[1] * X1 + R[2] + disp * t[0];
-  const float y = R[3] * X0 + R[4] * X1 + R[5] + disp * t[1];
-  const float z = R[6] * X0 + R[7] * X1 + R[8] + disp * t[2];
-  const bool bad = z < DROID_MIN_DEPTH;
-  const float d = bad ? 0.f : 1.0f / z;
+// 1 / z rounded to float.  From an fp64 z: the fp32 reciprocal refined by one Newton step in fp64 (relative error
+// 1e-7 -> 1e-14, as in linearize_pixel_d) instead of an fp64 division per edge and pixel.
+__device__ __forceinline__ float recip_f(float z) { return 1.0f / z; }
+__device__ __forceinline__ float recip_f(double z) {
+  const double d = (double)(1.0f / (float)z);
+  return (float)(d * (2.0 - z * d));
+}
+
+template <typename S>
+__device__ __forceinline__ PixLin jacobians_pixel(const Intr& K, const S* R, const S* t, S X0, S X1, float disp) {
+  const S x = R[0] * X0 + R[1] * X1 + R[2] + (S)disp * t[0];
+  const S y = R[3] * X0 + R[4] * X1 + R[5] + (S)disp * t[1];
+  const S z = R[6] * X0 + R[7] * X1 + R[8] + (S)disp * t[2];
+  const bool bad = z < (S)DROID_MIN_DEPTH;
+  const float d = bad ? 0.f : recip_f(z);
   PixLin L;
   L.valid = bad ? 0.f : 1.f;
   L.ru = 0.f;
   L.rv = 0.f;
-  pix_jacobians(K, x, y, d, disp, t[0], t[1], t[2], L);
+  pix_jacobians(K, (float)x, (float)y, d, disp, (float)t[0], (float)t[1], (float)t[2], L);
   return L;
 }
 

@@ -16,6 +16,7 @@ from oracle import geom
 SHAPES = [(1, 1), (1, 64), (9, 19), (17, 24), (30, 40), (31, 41), (48, 64), (96, 128)]
 ROT_DEG = (1.0, 20.0, 60.0)
 VARIANTS = ("negated", "nonunit", "shifted")
+ANISO = "anisoK"          # plain poses, intrinsics with fx, fy, cx, cy pairwise different (every other case: fx == fy == cx)
 PUSH = -3.0
 BETAS = (0.0, 0.3, 1.0)
 # depth thresholds: projmap's fall-back, reproject's depth-1 substitution, reproject's valid, projmap / frame_distance valid
@@ -25,6 +26,19 @@ Z_REPROJECT = (0.5 * geom.MIN_DEPTH, geom.MIN_DEPTH)
 
 def cap(pixels):
     return max(2, int(2e-4 * pixels))
+
+
+def aniso_K(H, W):
+    """fx, fy, cx, cy pairwise at least 10 % apart (of the larger) at every shape of the suites, none centred: a kernel
+    that reads one for another is wrong by that much."""
+    return np.array([0.9 * W, 0.62 * W, 0.38 * W + 0.5, 0.36 * H - 0.75], np.float32)
+
+
+def aniso_K_frames(H, W, n):
+    """per-frame intrinsics, each anisotropic, no frame a common multiple of another"""
+    f = np.arange(n)
+    s = np.stack([1.0 + 0.03 * (f % 5), 1.0 - 0.02 * (f % 3), 1.0 + 0.015 * (f % 4), 1.0 - 0.025 * (f % 7)], axis=1)
+    return (aniso_K(H, W)[None].astype(np.float64) * s).astype(np.float32)
 
 
 def wild_poses(prob, rng, rot_deg, push, variant="plain", push_frame=3):
@@ -61,10 +75,13 @@ class Case:
         seed = (H * 1009 + W * 31 + int(rot_deg) * 7) if seed is None else seed
         prob = synth.make_ba_problem(N=8, E=32, H=H, W=W, seed=seed)
         rng = np.random.default_rng(seed + 1)
-        self.poses = wild_poses(prob, rng, rot_deg, PUSH, variant)
+        self.poses = wild_poses(prob, rng, rot_deg, PUSH, "plain" if variant == ANISO else variant)
         self.disps = prob.disps
-        self.K = prob.intrinsics.astype(np.float32)
-        self.K_frames = np.stack([self.K * np.float32(1.0 + 0.01 * (f % 7)) for f in range(8)]).astype(np.float32)
+        if variant == ANISO:
+            self.K, self.K_frames = aniso_K(H, W), aniso_K_frames(H, W, 8)
+        else:
+            self.K = prob.intrinsics.astype(np.float32)
+            self.K_frames = np.stack([self.K * np.float32(1.0 + 0.01 * (f % 7)) for f in range(8)]).astype(np.float32)
         self.ii, self.jj = prob.ii, prob.jj
         st = np.array([2, 7, 4])
         self.ii_st = np.concatenate([prob.ii[:-3], st])          # reproject: the last three become stereo edges
@@ -83,10 +100,11 @@ class Case:
 
 
 def all_cases():
-    """Every shape at every rotation scale, and the three quaternion variants at a shape below one workgroup and at
-    the 12-workgroup shape of the other suites."""
+    """Every shape at every rotation scale, and the three quaternion variants and the anisotropic intrinsics at a
+    shape below one workgroup and at the 12-workgroup shape of the other suites."""
     out = [Case(H, W, r, "plain") for (H, W) in SHAPES for r in ROT_DEG]
     out += [Case(H, W, r, v) for (H, W) in ((9, 19), (48, 64)) for r in ROT_DEG for v in VARIANTS]
+    out += [Case(H, W, r, ANISO) for (H, W) in ((9, 19), (48, 64)) for r in ROT_DEG]
     return out
 
 
@@ -155,10 +173,12 @@ def depth_ladder():
 # frame_distance_matrix
 MATRIX_N = (1, 2, 31, 32, 33, 65)
 MATRIX_SHAPES = ((9, 19), (48, 64))
+MATRIX_ANISO = (33, 9, 19)       # one instance with aniso_K: two block columns of targets, the second ragged
 
 
-def matrix_case(n, H, W):
-    """n frames in use of a buffer of n + 3: wild poses at 20 degrees, one frame pushed, the spare frames filled too."""
+def matrix_case(n, H, W, aniso=False):
+    """n frames in use of a buffer of n + 3: wild poses at 20 degrees, one frame pushed, the spare frames filled too.
+    aniso: the intrinsics of aniso_K instead of the generator's (fx == fy == cx)."""
     nbuf = n + 3
     seed = 4000 + 10 * n + H
     prob = synth.make_ba_problem(N=nbuf, H=H, W=W, seed=seed, edges=(np.arange(1, nbuf), np.arange(nbuf - 1)))
@@ -166,7 +186,8 @@ def matrix_case(n, H, W):
     poses = wild_poses(prob, rng, 20.0, PUSH, "plain", push_frame=min(3, n - 1))
     # a trajectory this wild overlaps nowhere: pull the frames together so that both outcomes of the 0.75 test occur
     poses[:, :3] *= np.float32(0.35)
-    return dict(poses=poses, disps=prob.disps, K=prob.intrinsics.astype(np.float32), n=n, nbuf=nbuf)
+    K = aniso_K(H, W) if aniso else prob.intrinsics.astype(np.float32)
+    return dict(poses=poses, disps=prob.disps, K=K, n=n, nbuf=nbuf)
 
 
 def matrix_reference(mc, chunk=128):

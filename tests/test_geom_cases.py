@@ -60,6 +60,20 @@ def test_variants_change_the_poses_the_way_they_say():
     assert np.abs(a[2]["Z"] - b[2]["Z"]).max() < 1e-3
 
 
+def test_anisotropic_cases_have_four_different_intrinsics():
+    aniso = [c for c in CASES if c.variant == gc.ANISO]
+    assert sorted((c.H, c.W, c.rot_deg) for c in aniso) == sorted((H, W, r) for (H, W) in ((9, 19), (48, 64)) for r in gc.ROT_DEG)
+    for c in aniso:
+        plain = gc.Case(c.H, c.W, c.rot_deg, "plain")
+        assert np.array_equal(c.poses, plain.poses) and np.array_equal(c.target, plain.target)
+        for K in (c.K, *c.K_frames):
+            K = K.astype(np.float64)
+            assert all(abs(K[a] - K[b]) >= 0.1 * max(K[a], K[b]) for a in range(4) for b in range(a)), K
+        r = c.K_frames.astype(np.float64) / c.K_frames[0]
+        assert all(np.ptp(r[f]) > 5e-3 for f in range(1, 8))                # no frame a common multiple of frame 0
+    assert all(c.K[0] == c.K[1] == c.K[2] for c in CASES if c.variant != gc.ANISO)
+
+
 def test_depth_ladder_levels_decide_every_flag():
     L = gc.depth_ladder()
     lv = gc.LEVELS[L["level"]]
@@ -89,7 +103,17 @@ def test_depth_ladder_levels_decide_every_flag():
 @pytest.mark.parametrize("n", gc.MATRIX_N)
 @pytest.mark.parametrize("shape", gc.MATRIX_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_matrix_cases_decide_the_1000_pattern(n, shape):
-    mc = gc.matrix_case(n, *shape)
+    _matrix_case_decides(n, shape, gc.matrix_case(n, *shape))
+
+
+def test_anisotropic_matrix_case_decides_the_1000_pattern():
+    n, H, W = gc.MATRIX_ANISO
+    mc = gc.matrix_case(n, H, W, aniso=True)
+    assert np.array_equal(mc["K"], gc.aniso_K(H, W)) and np.array_equal(mc["poses"], gc.matrix_case(n, H, W)["poses"])
+    _matrix_case_decides(n, (H, W), mc)
+
+
+def _matrix_case_decides(n, shape, mc):
     ii, jj, parts, nband = gc.matrix_reference(mc)
     hw = shape[0] * shape[1]
     assert nband.sum() <= gc.cap(n * n * hw)

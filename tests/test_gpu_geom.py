@@ -393,9 +393,18 @@ def test_frame_distance_matrix_cases(backends, oracle, n, shape):
     (1e-5 of the largest entry that is not 1000: the same arithmetic in another kernel, whose FMA contraction is
     the compiler's), and the
     symmetrisation; the output is over-allocated and must stay untouched behind n * n."""
+    _check_matrix_case(backends, oracle, n, shape, gc.matrix_case(n, *shape))
+
+
+def test_frame_distance_matrix_anisotropic_case(backends, oracle):
+    """The same checks with fx, fy, cx, cy pairwise different (geom_cases.aniso_K) at n = 33."""
+    n, H, W = gc.MATRIX_ANISO
+    _check_matrix_case(backends, oracle, n, (H, W), gc.matrix_case(n, H, W, aniso=True))
+
+
+def _check_matrix_case(backends, oracle, n, shape, mc):
     torch = _torch()
     H, W = shape
-    mc = gc.matrix_case(n, H, W)
     ii, jj, parts, nband = gc.matrix_reference(mc)
     poses, disps, K = _dev(mc["poses"]), _dev(mc["disps"]), _dev(mc["K"])
     lib = backends._lib.load()

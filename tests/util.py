@@ -248,3 +248,37 @@ def stage_errors(oracle, p, stages, motion_only=False):
     err["state"] = max(et, er, ed)
     err["state_parts"] = (et, er, ed)
     return err
+
+
+def relative_state_error(p, got, ref):
+    """(translation, rotation, disparity) distance of the state `got` = (poses, disps) from `ref`, both one update of
+    the state of `p`, for scenes whose update is not small (tests/hard_scenes.py: a disparity may move by 10, where
+    the absolute |ddisp| of STAGE_BARS says nothing): per pixel |ddisp| / (|disp before| + |dz of ref|), per frame
+    ||dt|| / (||t before|| + ||step of ref||), and the rotation angle as it is.  A pixel or frame that `ref` leaves at
+    0 with a step of 0 has to be 0 in `got` as well (it counts as 1 otherwise)."""
+    p0, d0 = np.asarray(p.poses, np.float64), np.asarray(p.disps, np.float64)
+    gp, gd = (np.asarray(a, np.float64) for a in got)
+    rp, rd = (np.asarray(a, np.float64) for a in ref)
+
+    def rel(num, den):
+        return float(np.where(num == 0, 0.0, np.where(den > 0, num / np.where(den > 0, den, 1.0), 1.0)).max())
+
+    n = np.linalg.norm
+    et = rel(n(gp[:, :3] - rp[:, :3], axis=1), n(p0[:, :3], axis=1) + n(rp[:, :3] - p0[:, :3], axis=1))
+    er = float(quat_angle(gp[:, 3:], rp[:, 3:]).max())
+    ed = rel(np.abs(gd - rd), np.abs(d0) + np.abs(rd - d0))
+    return et, er, ed
+
+
+def stage_state_relative(oracle, p, stages, motion_only=False):
+    """relative_state_error of the state `stages` (run_ba_stages) ends in, against the oracle's fp64 solve,
+    back-substitution and retraction of the device's own system -- the comparison of stage_errors, in the metric for
+    scenes whose update is large."""
+    nbuf = p.disps.shape[0]
+    ph = oracle.BAPhases()
+    ph.build(*ba_args(p), 0, nbuf, motion_only)
+    n = 6 * (p.t1 - p.t0)
+    Hd, bd = stages["system"][:n], stages["system"][n]
+    lm, ep = float(np.float32(p.lm)), float(np.float32(p.ep))
+    poses, disps, _ = ph.finish(np.tril(Hd) + np.tril(Hd, -1).T, bd, lm, ep)
+    return relative_state_error(p, (stages["poses"], stages["disps"]), (poses, disps))
