@@ -52,6 +52,10 @@ void launch_depth_filter(const float* poses, const float* disps, const float* in
 // upsample.hip
 void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
                          bool half_mask, hipStream_t s);
+// graph_agg.hip
+size_t graph_mean_workspace_bytes(int E, int range);
+void launch_graph_mean(const void* src, const int64_t* index, void* out, int E, int64_t plane, int M, int range,
+                       int compact, bool half, int* groups_out, void* workspace, hipStream_t s);
 // chol.hip
 void launch_chol_pack(const double* A, const double* b, double* S, int n, int ld, hipStream_t s);
 void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
@@ -654,6 +658,48 @@ int droid_cvx_upsample(const float* data, const int64_t* ix, const void* mask, f
 }
 
 // ---------------------------------------------------------------------------- factor-graph edge selection
+// ------------------------------------------------------------------ graph aggregation
+// sizes droid_graph_mean and its workspace query check; <0 after fail()
+static int graph_mean_check(int E, int range) {
+  if (E < 0 || E > 65535) return fail(DROID_E_ARG, "graph_mean: bad %s", "E (0 .. 65535)");
+  if (range < 1 || range > DROID_GRAPH_MEAN_MAX_RANGE)
+    return fail(DROID_E_ARG, "graph_mean: bad %s", "range (1 .. 16384: the prepare step's tables live in LDS)");
+  return 0;
+}
+
+size_t droid_graph_mean_workspace_bytes(int E, int range) {
+  if (graph_mean_check(E, range)) return 0;
+  return graph_mean_workspace_bytes(E, range);
+}
+
+int droid_graph_mean(const void* src, const int64_t* index, void* out, int E, int64_t plane, int M, int range,
+                     int compact, int dtype, int* groups_out, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = graph_mean_check(E, range);
+  if (rc) return rc;
+  if (M < 1) return fail(DROID_E_ARG, "graph_mean: bad %s", "M (at least 1)");
+  if (compact != 0 && compact != 1) return fail(DROID_E_ARG, "graph_mean: bad %s", "compact (0 or 1)");
+  if (!compact && range != M) return fail(DROID_E_ARG, "graph_mean: %s", "dense mode (compact = 0) needs range == M");
+  if (plane < 1) return fail(DROID_E_ARG, "graph_mean: bad %s", "plane (at least 1)");
+  const int64_t lim = (int64_t)1 << 62;
+  if (plane > lim / M || (E > 0 && plane > lim / E))
+    return fail(DROID_E_ARG, "graph_mean: %s", "M * plane or E * plane exceeds the kernel's index range (2^62)");
+  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "graph_mean: bad %s", "dtype (f16 or f32)");
+  if (!out) return fail(DROID_E_ARG, "graph_mean: null %s", "pointer (out)");
+  if (E > 0 && (!src || !index)) return fail(DROID_E_ARG, "graph_mean: null %s", "pointer (src / index)");
+  hipStream_t s = (hipStream_t)stream;
+  if (E == 0) {   // every row is empty: no lists to build, no workspace needed
+    (void)hipMemsetAsync(out, 0, (size_t)M * (size_t)plane * (dtype == DROID_F16 ? 2 : 4), s);
+    if (groups_out) (void)hipMemsetAsync(groups_out, 0, sizeof(int), s);
+    return check_hip("graph_mean");
+  }
+  if (!workspace) return fail(DROID_E_ARG, "graph_mean: null %s", "workspace");
+  if (workspace_bytes < graph_mean_workspace_bytes(E, range))
+    return fail(DROID_E_WORKSPACE, "graph_mean: %s", "workspace too small");
+  if ((uintptr_t)workspace % 4 != 0) return fail(DROID_E_ARG, "graph_mean: %s", "workspace is not 4-byte aligned");
+  launch_graph_mean(src, index, out, E, plane, M, range, compact, dtype == DROID_F16, groups_out, workspace, s);
+  return check_hip("graph_mean");
+}
+
 // sizes every proximity entry point checks; <0 after fail()
 static int proximity_check(int t, int t0, int t1, int n_known, int cap) {
   if (t < 0 || t0 < 0 || t1 < 0) return fail(DROID_E_ARG, "proximity_edges: negative %s", "t / t0 / t1");

@@ -24,7 +24,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "corr_pyramid_forward",  # the last four are additions
            "proximity_edges",       # add_proximity_factors' edge selection, on the device
            "corr_volume_pyramid",   # CorrBlock.__init__ for a list of edges, in one launch
-           "upsample_disps", "cvx_upsample"]   # DepthVideo.upsample / droid_net.cvx_upsample, in one launch
+           "upsample_disps", "cvx_upsample",   # DepthVideo.upsample / droid_net.cvx_upsample, in one launch
+           "graph_mean", "scatter_mean"]       # GraphAgg's source-frame mean (torch_scatter.scatter_mean), no atomics
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
@@ -414,6 +415,96 @@ def cvx_upsample(data, mask):
     _lib.check(lib.droid_cvx_upsample(data.data_ptr(), None, mask.data_ptr(), out.data_ptr(), batch, batch, batch, ht, wd,
                                       _DT[mask.dtype], _stream()), "cvx_upsample")
     return out
+
+
+_gm_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of graph_mean / scatter_mean
+
+
+def _graph_mean_args(what, src, index, batched):
+    """The checks both entry points share, a caller's mistake named before the device is looked at.  Returns src as
+    [E, ...] rows (src[0] when `batched`: [1, E, ...])."""
+    if src.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{what}: src must be float16 or float32, got {src.dtype}")
+    if index.dtype != torch.int64:
+        raise RuntimeError(f"{what}: index must be int64 (torch.long), got {index.dtype}")
+    if torch.is_grad_enabled() and src.requires_grad:
+        raise RuntimeError(f"{what}: no autograd -- training keeps torch_scatter (inference only)")
+    for x, name in ((src, "src"), (index, "index")):
+        if not x.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be contiguous")
+    if batched and src.shape[0] != 1:
+        raise RuntimeError(f"{what}: batch must be 1, got {int(src.shape[0])}")
+    rows = src[0] if batched else src
+    if index.dim() != 1 or int(index.shape[0]) != int(rows.shape[0]):
+        raise RuntimeError(f"{what}: index must be [E] = [{int(rows.shape[0])}], one group per row of src, got "
+                           f"{tuple(index.shape)}")
+    for x, name in ((src, "src"), (index, "index")):
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
+    if index.device != src.device:
+        raise RuntimeError(f"{what}: index is on {index.device}, src on {src.device}")
+    return rows
+
+
+def _graph_mean_run(what, rows, batched, index, M, rng, compact):
+    lib = _lib.load()
+    dev = rows.device
+    E = int(rows.shape[0])
+    out = torch.empty(((1,) if batched else ()) + (M,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=dev)
+    plane = 1
+    for v in rows.shape[1:]:
+        plane *= int(v)
+    if M == 0 or plane == 0:
+        return out
+    ws, stream = None, _stream()
+    if E > 0:
+        nbytes = lib.droid_graph_mean_workspace_bytes(E, rng)   # 0 for sizes the call below refuses by name
+        key = (dev.index, stream)
+        ws = _gm_ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = _gm_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+    _lib.check(lib.droid_graph_mean(rows.data_ptr() if E else None, index.data_ptr() if E else None, out.data_ptr(),
+                                    E, plane, M, rng, compact, _DT[rows.dtype], None, _ptr(ws),
+                                    ws.numel() if ws is not None else 0, stream), what)
+    return out
+
+
+def graph_mean(net, ii, num_groups=None, nbuf=None):
+    """`GraphAgg.forward`'s source-frame mean (droid_slam/droid_net.py:63-67) with its `torch.unique` fused:
+    `_, ix = torch.unique(ii, return_inverse=True); net = scatter_mean(net, ix, dim=1)` becomes
+    `net = graph_mean(net, ii)`.  net [1, E, C, H, W] or [E, C, H, W], float16 or float32, contiguous; ii [E] int64.
+    Returns [1, M, C, H, W] or [M, C, H, W]: row g is the mean over the edges whose source is the g-th smallest distinct
+    frame.  M = num_groups when given (then the host reads nothing; rows beyond the distinct count are +0.0), else
+    torch.unique(ii).numel(), the reference's own synchronisation.  nbuf = the frame-buffer size (frames outside
+    [0, nbuf) are ignored); None reads int(ii.max()) + 1.  fp32 sums in edge order, no atomics: the same bits on every
+    run.  Contract: include/droid_backends_hip.h (droid_graph_mean, compact = 1).  Inference only.  An addition."""
+    if net.dim() not in (4, 5):
+        raise RuntimeError(f"graph_mean: net must be [1, E, C, H, W] or [E, C, H, W], got {tuple(net.shape)}")
+    batched = net.dim() == 5
+    rows = _graph_mean_args("graph_mean", net, ii, batched)
+    E = int(ii.shape[0])
+    rng = int(nbuf) if nbuf is not None else (int(ii.max()) + 1 if E else 1)
+    M = int(num_groups) if num_groups is not None else int(torch.unique(ii).numel())
+    if M < 0:
+        raise RuntimeError("graph_mean: num_groups must not be negative")
+    return _graph_mean_run("graph_mean", rows, batched, ii, M, max(rng, 1), 1)
+
+
+def scatter_mean(src, index, dim=1, dim_size=None):
+    """`torch_scatter.scatter_mean(src, index, dim=1)` in the one form `GraphAgg` calls it with
+    (`from droid_backends import scatter_mean` replaces the import): src [1, E, ...] with dim = 1, or [E, ...] with
+    dim = 0, float16 or float32, contiguous; index [E] int64.  Row r of the result is the mean of the entries with
+    index == r, a row without entries +0.0; rows = dim_size, or int(index.max()) + 1 (the read torch_scatter makes too).
+    Entries outside [0, rows) are ignored.  Contract: include/droid_backends_hip.h (droid_graph_mean, compact = 0).
+    Inference only: no autograd."""
+    if dim not in (0, 1) or src.dim() < dim + 1:
+        raise RuntimeError(f"scatter_mean: only dim = 1 on [1, E, ...] or dim = 0 on [E, ...] is supported, got dim = "
+                           f"{dim} on {tuple(src.shape)}")
+    rows = _graph_mean_args("scatter_mean", src, index, dim == 1)
+    M = int(dim_size) if dim_size is not None else (int(index.max()) + 1 if index.numel() else 0)
+    if M < 0:
+        raise RuntimeError("scatter_mean: dim_size must not be negative")
+    return _graph_mean_run("scatter_mean", rows, dim == 1, index, M, max(M, 1), 0)
 
 
 def _corr_dtype(t, name):

@@ -27,6 +27,7 @@ SYMBOLS = [
     "droid_frame_distance", "droid_frame_distance_matrix", "droid_projmap", "droid_iproj", "droid_depth_filter",
     "droid_proximity_workspace_bytes", "droid_proximity_edges",
     "droid_cvx_upsample",
+    "droid_graph_mean_workspace_bytes", "droid_graph_mean",
 ]
 
 DROID_F16, DROID_F32, DROID_F64 = 0, 1, 2
@@ -101,9 +102,12 @@ def load() -> ctypes.CDLL:
     lib.droid_proximity_edges.argtypes = ([vp] + [c_int] * 7 + [c_float, c_int, c_int, vp, vp, c_int, vp, vp, c_int,
                                                                 vp, c_int, vp, vp, sz, vp])
     lib.droid_cvx_upsample.argtypes = [vp] * 4 + [c_int] * 6 + [vp]
+    lib.droid_graph_mean_workspace_bytes.argtypes = [c_int, c_int]
+    lib.droid_graph_mean_workspace_bytes.restype = sz
+    lib.droid_graph_mean.argtypes = [vp, vp, vp, c_int, ctypes.c_int64] + [c_int] * 4 + [vp, vp, sz, vp]
     for s in SYMBOLS[2:]:
         if s not in ("droid_ba_workspace_bytes", "droid_ba_system", "droid_ba_packed_system", "droid_chol_scratch_doubles",
-                     "droid_proximity_workspace_bytes"):
+                     "droid_proximity_workspace_bytes", "droid_graph_mean_workspace_bytes"):
             getattr(lib, s).restype = c_int
     if lib.droid_abi_version() != 1:
         raise DroidBackendError("ABI version mismatch")

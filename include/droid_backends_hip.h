@@ -362,6 +362,48 @@ int droid_depth_filter(const float *poses, const float *disps, const float *intr
 int droid_cvx_upsample(const float *data, const int64_t *ix, const void *mask, float *out, int n, int nbuf_in,
                        int nbuf_out, int H, int W, int mask_dtype, void *stream);
 
+/* ------------------------------------------------------------------ graph aggregation */
+
+/* The source-frame mean of the update operator, `GraphAgg.forward` (droid_slam/droid_net.py:59-75):
+ *   _, ix = torch.unique(ii, return_inverse=True) ;  net = scatter_mean(net.view(batch, num, 128, ht, wd), ix, dim=1)
+ * (torch_scatter) in two launches on the stream, without atomics and without a host read.  Not one of the reference's
+ * nine operators.
+ * src [E, plane] and out [M, plane] of `dtype` (DROID_F16 or DROID_F32), contiguous; plane = C*H*W is any value >= 1.
+ * No alignment requirement on plane or on the pointers: where src or out is not 16-byte aligned, or the row pitch is
+ * not a multiple of 16 bytes, an element-wise path computes the same bits as the 16-byte path.
+ * index [E] int64 on the DEVICE.  The host never reads it, so it is checked on the device: an entry outside [0, range)
+ * belongs to no group and is ignored.
+ * Grouping.
+ *  compact = 0 (torch_scatter semantics; needs range == M): row r of out is the mean of the entries with index[e] == r;
+ *    a row without entries is +0.0.
+ *  compact = 1 (GraphAgg with its torch.unique fused; range = the frame-buffer size): row g is the mean of the entries
+ *    whose index is the g-th smallest distinct in-range value.  With fewer distinct values than M the remaining rows
+ *    are +0.0; with more, the groups from M onward are not written.
+ *  groups_out (device int, may be NULL) receives the number of distinct in-range values (dense mode: the rows that
+ *    have an entry), so that a caller can pass a known M without a host synchronisation and check it later.
+ * Arithmetic.  For a group with the entries e_0 < e_1 < ... (ascending e) and count n, per element:
+ *    acc = float(x[e_0]) ;  acc = acc + float(x[e_k]) for k = 1 .. n-1, in fp32, in that order ;
+ *    q = acc / float(n), one correctly rounded fp32 division ;  out = T(q), round to nearest even.
+ *  Half inputs are widened exactly, subnormals are kept, nothing is sanitised: NaN and inf propagate by IEEE rules and
+ *  a group holding a single -0.0 yields -0.0.  No atomics on out: the same bits on every run.  The bits of a group do
+ *  not depend on E, on the other groups or on where its entries sit among foreign ones, only on the order of its own
+ *  entries.  Per element |out - exact mean| <= (n + 2) * 2^-24 * (sum |x| / n), plus 2^-11 |mean| + 2^-25 for a half
+ *  output.  out is written completely (all M rows); src and index are only read.
+ * Limits, DROID_E_ARG with a message that names graph_mean and the argument: E outside 0 .. 65535 ; range < 1 or above
+ * DROID_GRAPH_MEAN_MAX_RANGE (the prepare step keeps a count, a presence bitmap and its prefix ranks over [0, range) in
+ * LDS) ; M < 1 ; compact not 0 / 1 ; compact = 0 with range != M ; plane < 1, or M * plane or E * plane beyond 2^62 ; a
+ * dtype other than F16 / F32 ; a null out, or a null src or index with E > 0 ; a null workspace with E > 0.  A workspace
+ * below droid_graph_mean_workspace_bytes(E, range) (host arithmetic: (range + 1 + E) ints; 0 for an E or range refused
+ * here): DROID_E_WORKSPACE.  All checks are host-side and precede any HIP call: sizes and dtype, then pointers, then
+ * the workspace.  E == 0 zero-fills out, writes 0 to groups_out, needs no workspace and returns 0.  Concurrent calls
+ * need separate workspaces.  The prepare step is one workgroup: up to 8192 entries it sorts the lists in LDS (a few
+ * microseconds); beyond, one thread per frame walks the index, sized for what a factor graph can hold and no more
+ * (milliseconds at E = 65535 with 16384 frames). */
+#define DROID_GRAPH_MEAN_MAX_RANGE 16384
+size_t droid_graph_mean_workspace_bytes(int E, int range);
+int droid_graph_mean(const void *src, const int64_t *index, void *out, int E, int64_t plane, int M, int range,
+                     int compact, int dtype, int *groups_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ factor-graph edge selection */
 
 /* The edge list `FactorGraph.add_proximity_factors` (droid_slam/factor_graph.py:315-379) hands to `add_factors`,
