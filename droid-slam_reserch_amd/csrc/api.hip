@@ -280,7 +280,8 @@ static int ba_view(BaView& v, void* ws, size_t ws_bytes, const BaDims& d) {
   if (d.E < 0 || d.nbuf <= 0 || d.H <= 0 || d.W <= 0) return fail(DROID_E_ARG, "ba: bad %s", "sizes");
   if (d.t0 < 0 || d.t1 <= d.t0 || d.t1 > d.nbuf) return fail(DROID_E_ARG, "ba: bad %s", "window [t0,t1)");
   if (d.M < 0 || d.M > d.nbuf) return fail(DROID_E_ARG, "ba: bad %s", "depth-slot count (eta rows)");
-  if (!d.motion_only && d.M == 0) return fail(DROID_E_ARG, "ba: %s", "eta has no rows");
+  // a rank of an edge-sharded call that owns no window frame and holds no edge has no depth slot: its build is zeros
+  if (!d.motion_only && d.M == 0 && d.E > 0) return fail(DROID_E_ARG, "ba: %s", "eta has no rows");
   if (!ws) return fail(DROID_E_ARG, "ba: null %s", "workspace");
   const size_t need = ba_carve(v, ws, d.E, d.nbuf, d.H, d.W, d.t0, d.t1, d.motion_only ? 0 : d.M);
   if (ws_bytes < need) return fail(DROID_E_WORKSPACE, "ba: %s", "workspace too small");
@@ -343,7 +344,7 @@ static int ba_build_impl(const float* poses, const float* disps, const float* in
   hints_of(v, workspace, false);
   if (!poses || !disps || !intrinsics) return fail(DROID_E_ARG, "ba: null %s", "state pointer");
   if (d.E > 0 && (!targets || !weights || !ii || !jj)) return fail(DROID_E_ARG, "ba: null %s", "edge data");
-  if (!d.motion_only && (!eta || !disps_sens)) return fail(DROID_E_ARG, "ba: null %s", "eta/disps_sens");
+  if (!d.motion_only && d.M > 0 && (!eta || !disps_sens)) return fail(DROID_E_ARG, "ba: null %s", "eta/disps_sens");
   enqueue_build(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, d.motion_only != 0,
                 (hipStream_t)stream, [] {});
   return check_hip("ba_build");
@@ -414,6 +415,10 @@ int droid_ba_overlap_plan(int t0, int t1, int max_chunks, int* nchunks_out, size
   return DROID_OK;
 }
 
+int droid_ba_overlap_available(int t0, int t1) {
+  return (t1 > t0 && chol_overlap_available(6 * (t1 - t0))) ? 1 : 0;
+}
+
 int droid_ba_unpack_chunk(int E, int nbuf, int H, int W, int M, int t0, int t1, int chunk, int max_chunks, float lm,
                           float ep, int epoch, void* workspace, size_t workspace_bytes, void* stream) {
   BaView v;
@@ -473,6 +478,8 @@ int droid_ba(float* poses, float* disps, const float* intrinsics, const float* d
              const int64_t* jj, int E, int nbuf, int H, int W, int M, int t0, int t1,
              int iterations, float lm, float ep, int motion_only, float* dx_out, float* dz_out,
              void* workspace, size_t workspace_bytes, void* stream) {
+  // one rank owns the whole window (t1 > t0): there is at least one depth slot
+  if (!motion_only && M == 0 && t1 > t0) return fail(DROID_E_ARG, "ba: %s", "eta has no rows");
   int rc = droid_ba_prepare(ii, jj, E, nbuf, H, W, M, t0, t1, 0, nbuf, motion_only, workspace,
                             workspace_bytes, stream);
   if (rc) return rc;

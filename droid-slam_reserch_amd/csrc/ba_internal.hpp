@@ -282,5 +282,8 @@ void launch_chol_solve(const CholSystem& c, double lm, double ep, hipStream_t s,
 // system, nothing was launched); launch_chol_backsolve(c, true, s) follows it.
 void launch_unpack_cols(const BaView& v, int J0, int J1, double lm, double ep, int epoch, hipStream_t s);
 bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s);
+// whether launch_chol_factor_overlap can take a system of n unknowns on the current device: from n, the device and the
+// process-wide switches alone, so that every rank of a group answers alike
+bool chol_overlap_available(int n);
 
 }  // namespace droid

@@ -1517,14 +1517,26 @@ static bool launch_factor_grid(const void* fn, CholSystem c, double lm, double e
   return launch_spinning_grid(fn, chol_tiles(c.n) < (size_t)cap ? (int)chol_tiles(c.n) : cap, 512, args, s);
 }
 
+// Workgroups of the overlap grid for a system of n unknowns, 0: the per-tile kernel cannot take it.  Only what every
+// rank of a group shares goes in: the system size, the device and the process-wide switches.
+static int chol_overlap_cap(int n) {
+  const CholSwitches& sw = chol_switches();
+  const int nb = (n + NB - 1) / NB;
+  if (n <= 0 || sw.cooperative || sw.multi_launch || nb < 2) return 0;
+  const int resident = chol_resident_workgroups();
+  if (resident < 8 || chol_tiles(n) > (size_t)10 * resident) return 0;
+  const int cap = resident - (sw.overlap_reserve > 0 ? sw.overlap_reserve : 0);
+  return (cap >= 8 && chol_tiles(n) <= (size_t)10 * cap) ? cap : 0;
+}
+bool chol_overlap_available(int n) { return chol_overlap_cap(n) > 0; }
+
 // Overlap mode: the per-tile single-launch kernel only (false when it cannot be used: the caller then unpacks the whole
 // system and solves the ordinary way).  `ready` [block columns] / `epoch`: see the kernel; the unpack kernel damps, so
 // lm = ep = 0 here.  The grid leaves `overlap_reserve` CUs free for the collective and the unpack kernels.
 bool launch_chol_factor_overlap(const CholSystem& c, const int* ready, int epoch, hipStream_t s) {
-  const CholSwitches& sw = chol_switches();
-  if (c.n <= 0 || !ready || sw.cooperative) return false;
-  const int cap = chol_single_launch(c) - (sw.overlap_reserve > 0 ? sw.overlap_reserve : 0);
-  if (cap < 8 || chol_tiles(c.n) > (size_t)10 * cap) return false;
+  if (!ready || (c.ld % 16) != 0 || (reinterpret_cast<uintptr_t>(c.S) % 128) != 0) return false;
+  const int cap = chol_overlap_cap(c.n);
+  if (cap == 0) return false;
   return launch_factor_grid((const void*)chol_factor_persistent_kernel<true>, c, 0.0, 0.0, ready, epoch, cap, s);
 }
 

@@ -153,6 +153,10 @@ class BaBinding:
         _lib.check(self.lib.droid_ba_solve_update(*self._update_args(p), float(lm), float(ep), int(motion_only),
                                                   *self._out(dx, dz), *self._ws()), "ba_solve_update")
 
+    def overlap_available(self):
+        """Whether solve_update_overlap takes a window of this size on this device: the same answer on every rank."""
+        return bool(self.lib.droid_ba_overlap_available(self.dims[5], self.dims[6]))
+
     def overlap_plan(self, max_chunks):
         """[(first, last)] element ranges of `packed()`, one per chunk (whole block rows of the system, in order)."""
         nc = ctypes.c_int(0)

@@ -87,6 +87,10 @@ class HipBackend:
     # chunks = collectives per iteration: each costs its own launch + synchronisation latency on the wire, so few
     OVERLAP_MAX_CHUNKS = int(__import__("os").environ.get("DROID_BA_OVERLAP_CHUNKS", "4"))
 
+    def overlap_available(self):
+        """Whether the overlap is taken for this window: decided from what every rank shares (ShardedBA.run)."""
+        return self.binding.overlap_available()
+
     def overlap_plan(self):
         """[(first, last)] element ranges of `self.packed`, one per chunk (whole block rows of the system, in order)."""
         return self.binding.overlap_plan(self.OVERLAP_MAX_CHUNKS)
@@ -138,8 +142,11 @@ class ShardedBA:
         own = (0, nbuf) if own is None else own
         be = self.backend
         be.prepare(p, t0, t1, own, motion_only)
+        # Every rank of the group must issue the same collectives, so whether an iteration is cut into chunks depends
+        # only on what the ranks share: the overlap flag, the world size, motion_only and the system size (through
+        # overlap_available: window size, device and process-wide solver switches) -- never on the rank's own edges.
         use_overlap = self.overlap and world > 1 and hasattr(be, "solve_update_overlap") and not motion_only \
-            and int(p.ii.shape[0]) > 0
+            and be.overlap_available()
         for it in range(int(iterations)):
             if use_overlap:
                 packed = be.build_packed(p, motion_only)
@@ -148,18 +155,20 @@ class ShardedBA:
                     self._side = torch.cuda.Stream()
                 built = torch.cuda.Event()
                 built.record(main)
-                if be.solve_update_overlap(p, it + 1, motion_only):      # main stream: waits chunk by chunk on the device
-                    with torch.cuda.stream(self._side):
-                        self._side.wait_event(built)
-                        for c, (a, b) in enumerate(be.overlap_plan()):
-                            dist.all_reduce(packed[a:b], op=dist.ReduceOp.SUM, group=self.group)
+                # main stream: the solve waits chunk by chunk on the device.  A rank without edges cannot spin (the
+                # solver scratch is preset by a build with edges): it reduces the same chunks, then solves the ordinary
+                # way; so does a rank whose launch was refused after all.
+                spinning = int(p.ii.shape[0]) > 0 and be.solve_update_overlap(p, it + 1, motion_only)
+                with torch.cuda.stream(self._side):
+                    self._side.wait_event(built)
+                    for c, (a, b) in enumerate(be.overlap_plan()):
+                        dist.all_reduce(packed[a:b], op=dist.ReduceOp.SUM, group=self.group)
+                        if spinning:
                             be.unpack_chunk(c, lm, ep, it + 1)
-                    main.wait_stream(self._side)     # the next build clears the packed system
-                    continue
-                use_overlap = False                                      # system too small / solver mode: ordinary path
-                dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=self.group)
-                be.unpack(motion_only)
-                be.solve_update(p, lm, ep, motion_only)
+                main.wait_stream(self._side)     # the next build clears the packed system
+                if not spinning:
+                    be.unpack(motion_only)
+                    be.solve_update(p, lm, ep, motion_only)
                 continue
             if world > 1 and hasattr(be, "build_packed"):
                 # the build kernels add straight into the packed triangle: one collective on a contiguous tensor,

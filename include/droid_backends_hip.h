@@ -168,6 +168,9 @@ int droid_ba(float *poses, float *disps, const float *intrinsics, const float *d
  *
  * own0/own1: the frames whose depth maps this rank owns.  Edges passed to a rank must all have
  * ii in [own0,own1); window frames outside it create no depth slot here.  Single GPU: 0, nbuf.
+ * A rank whose range holds no window frame and that has no edge (more ranks than source frames) passes E = 0, M = 0,
+ * eta = NULL: its build writes zeros, its solve_update retracts the poses like every other rank's.  M = 0 with edges
+ * is refused (DROID_E_ARG), unless motion_only.
  *
  * droid_ba_prepare: once per call -- depth-slot table, CSR of edges by source frame.
  * droid_ba_build:   one linearisation: writes this rank's contribution to the reduced camera
@@ -219,7 +222,15 @@ int droid_ba_unpack_system(int E, int nbuf, int H, int W, int M, int t0, int t1,
  * epoch = 1, 2, ... within one droid_ba_prepare (which resets the published epochs).  The spinning grid leaves
  * DROID_OVERLAP_RESERVE_CUS (default 32) compute units free for the collective's kernels.  Returns DROID_E_ARG
  * when the single-launch solver cannot run this system (then: droid_ba_unpack_system + droid_ba_solve_update).
- * Rehearsed with two ranks on one GPU (gloo) and with eight in-process shards; NOT yet measured over RCCL. */
+ * Rehearsed with two ranks on one GPU (gloo) and with eight in-process shards; NOT yet measured over RCCL.
+ *
+ * Every rank of a group must issue the same collectives, so whether an iteration is cut into chunks may depend only on
+ * what the ranks share.  droid_ba_overlap_available answers from the window size, the current device and the
+ * process-wide solver switches alone (1: droid_ba_solve_update_overlap takes such a system, 0: it would return
+ * DROID_E_ARG); it reads no workspace.  A rank WITHOUT edges cannot spin (droid_ba_solve_update_overlap needs the
+ * preset of a build with edges): it all-reduces the same chunks as its peers, then calls droid_ba_unpack_system and
+ * droid_ba_solve_update. */
+int droid_ba_overlap_available(int t0, int t1);
 int droid_ba_overlap_plan(int t0, int t1, int max_chunks, int *nchunks_out, size_t *packed_offsets);
 int droid_ba_unpack_chunk(int E, int nbuf, int H, int W, int M, int t0, int t1, int chunk, int max_chunks, float lm,
                           float ep, int epoch, void *workspace, size_t workspace_bytes, void *stream);

@@ -67,17 +67,18 @@ GRAPHS = {
 }
 
 
-def predicted_classes(p, S2_MAXE=16, SW_MID=256, SW_BIG=512, SLOT_MAXE=128):
+def predicted_classes(p, S2_MAXE=16, SW_MID=256, SW_BIG=512, SLOT_MAXE=128, own=None):
     """Host restatement of ba_prep_kernel's slot classes (used to write the table above; the tests assert what the
-    DEVICE reports, not this)."""
+    DEVICE reports, not this).  own: the frame range of a shard whose edges `p` holds (default: the whole buffer)."""
     nbuf, H, W = p.disps.shape
-    kx = np.unique(np.concatenate([np.arange(p.t0, p.t1), p.ii]))
+    w0, w1 = (p.t0, p.t1) if own is None else (max(p.t0, own[0]), min(p.t1, own[1]))
+    kx = np.unique(np.concatenate([np.arange(w0, max(w0, w1)), p.ii])).astype(np.int64)
     M, E = len(kx), len(p.ii)
     wide = M > 0 and E >= 12 * M and (H * W) % 32 == 0
     out = []
     for f in kx:
         ne = int((p.ii == f).sum())
-        nent = int(p.t0 <= f < p.t1) + int(((p.ii == f) & (p.jj >= p.t0) & (p.jj < p.t1)).sum())
+        nent = int(w0 <= f < w1) + int(((p.ii == f) & (p.jj >= p.t0) & (p.jj < p.t1)).sum())
         rows = 6 * nent + 1
         if nent == 0 or ne <= S2_MAXE:
             out.append(0)

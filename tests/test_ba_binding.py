@@ -59,6 +59,7 @@ def test_dimensions_reach_every_function_in_the_header_s_order(binding):
     b.build(p, False, packed=True)
     b.unpack_system(False)
     b.solve_update(p, 0.25, 0.5, False, dx, dz)
+    b.overlap_available()
     b.overlap_plan(6)
     b.unpack_chunk(2, 6, 0.25, 0.5, 9)
     b.solve_update_overlap(p, 9, False, dx, dz)

@@ -141,6 +141,16 @@ STAGE_BARS = {
 PACKED_BAR = 1e-12   # build_packed + unpack vs build: the same sums in another order of the fp64 atomics
 
 
+def packed_column_bases(n, nb=64):
+    """Element offset of every block column of the packed system of n unknowns, and the total behind the last: the
+    layout include/droid_backends_hip.h documents (block column J = rows 64 J .. n, row n = rhs, as rows of w_J doubles;
+    w_J = 64, the last one n - 64 J)."""
+    bases = [0]
+    for J in range((n + nb - 1) // nb):
+        bases.append(bases[-1] + (n + 1 - nb * J) * min(nb, n - nb * J))
+    return bases
+
+
 def scaled_system_errors(Hd, bd, Ho, bo):
     """Entry-wise distance of a reduced system (Hd, bd) from the reference (Ho, bo), lower triangles.  The Schur
     complement is PSD, so |H_ab| <= sqrt(H_aa H_bb): scaling by the reference's diagonal bounds every entry by 1 and
@@ -177,11 +187,12 @@ def damped_solve(H, b, lm, ep):
     return np.linalg.solve(A, b)
 
 
-def run_ba_stages(backends, p, torch, motion_only=False, packed=False):
+def run_ba_stages(backends, p, torch, motion_only=False, packed=False, own=None):
     """One Gauss-Newton iteration through the phase ABI on a workspace of its own, with launch hints of its own (a
     BaBinding): droid_ba_prepare, droid_ba_build (its system copied before the solve factors it in place), optionally
     droid_ba_build_packed + droid_ba_unpack_system (copied too), droid_ba_solve_update.  Returns the copies, the
-    state after the update, dx, the header words and the hint words {tag, slots of Schur class 3}."""
+    state after the update, dx, the header words and the hint words {tag, slots of Schur class 3}.
+    own: the frame range handed to droid_ba_prepare (default: the whole buffer, a single GPU)."""
     from droid_backends.ba_binding import BAProblemDev, BaBinding
     d = BAProblemDev(**to_dev(p, torch))
     b = BaBinding(status_mirror=False, headroom=(1, 0))     # a zeroed workspace of exactly the size asked for
@@ -192,7 +203,7 @@ def run_ba_stages(backends, p, torch, motion_only=False, packed=False):
     dz = torch.zeros((max(M, 1), H * W), dtype=torch.float32, device="cuda")
     system = lambda: b.system().view(n + 1, -1)[:, :n].cpu().numpy().copy()
     try:
-        b.prepare(d, (0, nbuf), motion_only)
+        b.prepare(d, (0, nbuf) if own is None else own, motion_only)
         b.build(d, motion_only)
         torch.cuda.synchronize()
         hw = b.HINT_WORD
@@ -211,6 +222,73 @@ def run_ba_stages(backends, p, torch, motion_only=False, packed=False):
     return out
 
 
+def shard_of(p, ranges, rank):
+    """The arrays rank `rank` of `ranges` holds, as a problem of its own (ba_driver.shard_problem): its edges and eta
+    rows, the replicated state; `.own` = its frame range."""
+    import copy
+    from droid_backends import ba_driver
+    sh = ba_driver.shard_problem(p, ranges, rank)
+    q = copy.copy(p)
+    q.targets, q.weights, q.eta, q.ii, q.jj = sh["targets"], sh["weights"], sh["eta"], sh["ii"], sh["jj"]
+    q.own = tuple(int(x) for x in sh["own"])
+    return q
+
+
+def run_shard_stages(backends, p, ranges, torch, motion_only=False):
+    """One Gauss-Newton iteration of every shard of `p` (ranges: [(f0, f1)] per rank), the way the ranks of an
+    edge-sharded call run it, in one process: per rank a zeroed workspace of its own (a BaBinding), droid_ba_prepare
+    with its range, droid_ba_build and droid_ba_build_packed + droid_ba_unpack_system, each system copied before
+    anything factors it; the packed tensors are summed on the device in rank order (what the all-reduce does); every
+    rank copies the sum in, unpacks it (copied: the system it solves) and runs droid_ba_solve_update.
+    Returns per rank: shard (shard_of), own, system, system_packed, packed, system_sum, hdr, hint, status, M, dx, dz,
+    poses, disps."""
+    from droid_backends.ba_binding import BAProblemDev, BaBinding
+    n = 6 * (p.t1 - p.t0)
+    ranks = []
+    try:
+        for r in range(len(ranges)):
+            q = shard_of(p, ranges, r)
+            d = BAProblemDev(**to_dev(q, torch))
+            b = BaBinding(status_mirror=False, headroom=(1, 0))     # a zeroed workspace of exactly the size asked for
+            ranks.append((q, d, b))
+            E, nbuf, H, W, M, t0, t1 = b.begin(d, p.t0, p.t1, motion_only)
+            b.buf.zero_()
+        outs = []
+        total = None
+        for q, d, b in ranks:
+            system = lambda b=b: b.system().view(n + 1, -1)[:, :n].cpu().numpy().copy()
+            b.prepare(d, q.own, motion_only)
+            b.build(d, motion_only)
+            torch.cuda.synchronize()
+            hw = b.HINT_WORD
+            out = dict(shard=q, own=q.own, system=system(), hdr=b.header(),
+                       hint=(int(b.mirror[hw]), int(b.mirror[hw + 1])))
+            b.build(d, motion_only, packed=True)
+            packed = b.packed().clone()
+            b.unpack_system(motion_only)
+            torch.cuda.synchronize()
+            out.update(system_packed=system(), packed=packed.cpu().numpy())
+            total = packed if total is None else total + packed
+            outs.append(out)
+        for (q, d, b), out in zip(ranks, outs):
+            M, HW = b.dims[4], b.dims[2] * b.dims[3]
+            dx = torch.zeros((p.t1 - p.t0, 6), dtype=torch.float32, device="cuda")
+            dz = torch.zeros((max(M, 1), HW), dtype=torch.float32, device="cuda")
+            b.packed().copy_(total)
+            b.unpack_system(motion_only)
+            torch.cuda.synchronize()
+            out["system_sum"] = b.system().view(n + 1, -1)[:, :n].cpu().numpy().copy()
+            b.solve_update(d, p.lm, p.ep, motion_only, dx, dz)
+            torch.cuda.synchronize()
+            st, m = b.status()
+            out.update(status=st, M=m, dx=dx.cpu().numpy(), dz=dz.cpu().numpy()[:M], poses=d.poses.cpu().numpy(),
+                       disps=d.disps.cpu().numpy())
+    finally:
+        for _, _, b in ranks:
+            b.close()
+    return outs
+
+
 def slot_classes(stages, motion_only=False):
     """Schur classes the device served, from the header words and the hint words run_ba_stages read."""
     hdr, (tag, n3) = stages["hdr"], stages["hint"]
@@ -222,13 +300,17 @@ def slot_classes(stages, motion_only=False):
     return {c for c, k in enumerate(counts) if k > 0}
 
 
-def stage_errors(oracle, p, stages, motion_only=False):
+def stage_errors(oracle, p, stages, motion_only=False, own=None, solved=None):
     """Errors of every stage of `stages` (run_ba_stages) against the oracle from the same inputs:
     build (scaled entry-wise, zero blocks), packed build vs build, solve (dx vs an fp64 solve of the device's own
-    system) and back-substitution + retraction (the oracle's, applied to the device's own system)."""
+    system) and back-substitution + retraction (the oracle's, applied to the device's own system).
+    A shard (run_shard_stages): `p` holds the rank's own arrays, `own` its frame range -- the oracle then builds that
+    rank's partial system and keeps that rank's depth slots -- and `solved` is the system the rank factored, the sum
+    over the ranks ([n + 1, n], row n = rhs), which the solve and the back-substitution are judged on."""
     nbuf = p.disps.shape[0]
+    own = (0, nbuf) if own is None else own
     ph = oracle.BAPhases()
-    Ho, bo = ph.build(*ba_args(p), 0, nbuf, motion_only)
+    Ho, bo = ph.build(*ba_args(p), int(own[0]), int(own[1]), motion_only)
     sysd = stages["system"]
     n = Ho.shape[0]
     Hd, bd = sysd[:n], sysd[n]
@@ -238,6 +320,8 @@ def stage_errors(oracle, p, stages, motion_only=False):
         e = scaled_system_errors(sp[:n], sp[n], Hd, bd)
         err["packed"] = max(e["H"], e["b"])
         err["packed_stray"] = e["stray"] + e["dead"]
+    if solved is not None:
+        Hd, bd = solved[:n], solved[n]
     x = damped_solve(Hd, bd, p.lm, p.ep)
     err["dx"] = float(np.abs(stages["dx"].reshape(-1) - x).max() / max(np.abs(x).max(), 1e-300))
     lm, ep = float(np.float32(p.lm)), float(np.float32(p.ep))
