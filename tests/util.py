@@ -187,17 +187,26 @@ def damped_solve(H, b, lm, ep):
     return np.linalg.solve(A, b)
 
 
-def run_ba_stages(backends, p, torch, motion_only=False, packed=False, own=None):
+def run_ba_stages(backends, p, torch, motion_only=False, packed=False, own=None, binding=None, fill="zero"):
     """One Gauss-Newton iteration through the phase ABI on a workspace of its own, with launch hints of its own (a
     BaBinding): droid_ba_prepare, droid_ba_build (its system copied before the solve factors it in place), optionally
     droid_ba_build_packed + droid_ba_unpack_system (copied too), droid_ba_solve_update.  Returns the copies, the
-    state after the update, dx, the header words and the hint words {tag, slots of Schur class 3}.
-    own: the frame range handed to droid_ba_prepare (default: the whole buffer, a single GPU)."""
+    state after the update, dx, dz, the header words and the hint words {tag, slots of Schur class 3}.
+    own: the frame range handed to droid_ba_prepare (default: the whole buffer, a single GPU).
+    binding: a BaBinding the caller owns (not closed here), already reserved to at least the bytes this problem needs,
+    so that several runs share one workspace (tests/test_gpu_workspace_history.py); default: one of its own.
+    fill: what happens to the workspace before droid_ba_prepare -- "zero": zeroed (the default), "ff": every byte 0xFF
+    (NaN as fp32 and fp64, -1 as an int), "keep": left as the previous run through `binding` left it."""
     from droid_backends.ba_binding import BAProblemDev, BaBinding
+    assert fill in ("zero", "ff", "keep"), fill
     d = BAProblemDev(**to_dev(p, torch))
-    b = BaBinding(status_mirror=False, headroom=(1, 0))     # a zeroed workspace of exactly the size asked for
+    # default: a zeroed workspace of exactly the size asked for
+    b = BaBinding(status_mirror=False, headroom=(1, 0)) if binding is None else binding
     E, nbuf, H, W, M, t0, t1 = b.begin(d, p.t0, p.t1, motion_only)
-    b.buf.zero_()
+    if fill == "zero":
+        b.buf.zero_()
+    elif fill == "ff":
+        b.buf.fill_(0xFF)
     n = 6 * (t1 - t0)
     dx = torch.zeros((t1 - t0, 6), dtype=torch.float32, device="cuda")
     dz = torch.zeros((max(M, 1), H * W), dtype=torch.float32, device="cuda")
@@ -217,8 +226,10 @@ def run_ba_stages(backends, p, torch, motion_only=False, packed=False, own=None)
         torch.cuda.synchronize()
         st, m = b.status()
     finally:
-        b.close()
-    out.update(status=st, M=m, dx=dx.cpu().numpy(), poses=d.poses.cpu().numpy(), disps=d.disps.cpu().numpy())
+        if binding is None:
+            b.close()
+    out.update(status=st, M=m, dx=dx.cpu().numpy(), dz=dz.cpu().numpy()[:M], poses=d.poses.cpu().numpy(),
+               disps=d.disps.cpu().numpy())
     return out
 
 
