@@ -572,6 +572,12 @@ int droid_ba_attach_status_mirror(const void* workspace, int* mirror) {
   return DROID_OK;
 }
 
+int droid_test_wave_reduce32(const float* in, float* out, void* stream) {
+  if (!in || !out) return fail(DROID_E_ARG, "test_wave_reduce32: null %s", "pointer");
+  launch_wave_reduce32_test(in, out, (hipStream_t)stream);
+  return check_hip("test_wave_reduce32");
+}
+
 size_t droid_chol_scratch_doubles(int n) { return CholSystem::scratch_doubles(n); }
 
 int droid_chol_solve(const double* A, const double* b, double* x, int n, double* scratch,

@@ -9,6 +9,7 @@ namespace droid {
 constexpr int LIN_THREADS = 256;
 constexpr int LIN_PPT = 2;                       // pixels per thread per chunk
 constexpr int LIN_CP = LIN_THREADS * LIN_PPT;    // pixels per workgroup chunk
+constexpr int LIN_WAVES = LIN_THREADS / 64;      // waves per workgroup: each leaves its own partial sums of a chunk
 constexpr int CHOL_NB = 64;                      // Cholesky block size
 // row pitch of the augmented system in doubles: 128-byte rows, so 64-column tiles never share a cache line
 __host__ __device__ inline int chol_ld(int n) { return (n + 1 + 15) & ~15; }
@@ -84,7 +85,8 @@ struct BaView {
   int* gt_ptr;             // [nbuf+2] first partial-sum tile of a slot served by ba_schur2_kernel (exclusive scan)
   double* Gpart;           // [tiles][s2_split][256] fp64 partial sums of those slots' Gram tiles, one per pixel range
   int s2_split;            // pixel ranges per slot of ba_schur2_kernel
-  float* Hpart;            // [E][nch][32] per-(edge,chunk) partial Hjj (21) + vj (6)
+  float* Hpart;            // [E][nch][LIN_WAVES][32] per-(edge, chunk, wave of the chunk's workgroup) partial Hjj (21) + vj (6),
+                           // words 27..31 zero; the assemble step adds the waves of a chunk in fp32, the chunks in fp64
   float* Q;                // [M][HW] 1/C
   float* w;                // [M][HW]
   float* Erows;            // unused (nullptr): sparse slots recompute their E rows where they are consumed
@@ -153,7 +155,7 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
   v.gt_ptr = static_cast<int*>(take(sizeof(int) * (nbuf + 2)));
   v.cls_list = static_cast<int*>(take(sizeof(int) * 2 * (nbuf + 2)));
   v.xtmp = static_cast<int*>(take(sizeof(int) * 3 * ((size_t)E + 1)));
-  v.Hpart = static_cast<float*>(take(sizeof(float) * ((size_t)E * v.nch * 32 + 32)));
+  v.Hpart = static_cast<float*>(take(sizeof(float) * ((size_t)E * v.nch * LIN_WAVES * 32 + 32)));
   v.Q = static_cast<float*>(take(sizeof(float) * ((size_t)M * v.HW + 4)));
   v.w = static_cast<float*>(take(sizeof(float) * ((size_t)M * v.HW + 4)));
   v.Erows = nullptr;  // E rows are recomputed where they are consumed, never stored ...
@@ -256,6 +258,8 @@ struct CholSystem {
 };
 
 // kernels' launchers (ba_kernels.hip / chol.hip)
+// one wave through the linearisation's wave_reduce32: in [64][32] (lane, value) -> out [64] (what each lane returns)
+void launch_wave_reduce32_test(const float* in, float* out, hipStream_t s);
 void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStream_t s);
 // multi-GPU: expand the (all-reduced) packed system into the pitched matrix the solver factors in place
 void launch_unpack_system(const BaView& v, hipStream_t s);

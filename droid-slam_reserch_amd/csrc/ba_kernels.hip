@@ -68,48 +68,68 @@ __device__ void block_exscan(int* data, int L, int* lds, int* total) {
 // Sum 32 per-lane values over the 64 lanes of a wave with a halving butterfly (31 exchanges
 // instead of 32 x 6).  On return lane l holds the wave total of value
 // idx = bit5 + 2*bit4 + 4*bit3 + 8*bit2 + 16*bit1 of l (both lanes of a bit0 pair hold it).
+//
+// Every level pairs lane l with lane l ^ bit: the half of the lanes with the bit clear keeps the even value of a
+// pair and is sent the partner's, the other half the odd one, and each adds the two.  All exchanges stay in the
+// register file (none goes through the LDS crossbar, none waits on lgkmcnt):
+//   ^32, ^16  v_permlane32_swap / v_permlane16_swap of (v[2i], v[2i+1]): the swap IS the keep/send selection --
+//             afterwards the two registers hold {own, partner's} of the value a lane keeps, in either order
+//   ^8, ^4    two DPP moves whose bank mask (banks = 4 lanes) writes one half of the lanes each and leaves the own
+//             value in the other half: row_ror:8; row_shl:4 (lanes with bit 2 clear read lane + 4) / row_shr:4
+//   ^2, ^1    quad_perm (a bank mask cannot tell the lanes of a quad apart: one select pair at ^2)
+// fp32 addition is commutative, so each lane's total has the bits of keep + received whichever register holds which.
+template <int CTRL, int BANKS>
+__device__ __forceinline__ float dpp_move(float old, float src) {  // lanes of BANKS: src of the DPP source lane; others: old
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(src), CTRL, 0xf, BANKS, false));
+}
 __device__ __forceinline__ float wave_reduce32(float (&v)[32]) {
+  constexpr int ROW_SHL4 = 0x104, ROW_SHR4 = 0x114, ROW_ROR8 = 0x128, QUAD_XOR2 = 0x4E, QUAD_XOR1 = 0xB1;
   const int lane = threadIdx.x & 63;
 #pragma unroll
   for (int i = 0; i < 16; i++) {
-    const bool hi = lane & 32;
-    float keep = hi ? v[2 * i + 1] : v[2 * i];
-    float send = hi ? v[2 * i] : v[2 * i + 1];
-    v[i] = keep + __shfl_xor(send, 32);
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[2 * i]), __float_as_uint(v[2 * i + 1]), false, false);
+    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) {
-    const bool hi = lane & 16;
-    float keep = hi ? v[2 * i + 1] : v[2 * i];
-    float send = hi ? v[2 * i] : v[2 * i + 1];
-    v[i] = keep + __shfl_xor(send, 16);
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[2 * i]), __float_as_uint(v[2 * i + 1]), false, false);
+    v[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   }
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    const bool hi = lane & 8;
-    float keep = hi ? v[2 * i + 1] : v[2 * i];
-    float send = hi ? v[2 * i] : v[2 * i + 1];
-    v[i] = keep + __shfl_xor(send, 8);
+    const float a = dpp_move<ROW_ROR8, 0x3>(v[2 * i + 1], v[2 * i]);   // bit 3 clear: partner's even; set: own odd
+    const float b = dpp_move<ROW_ROR8, 0xC>(v[2 * i], v[2 * i + 1]);   // bit 3 clear: own even; set: partner's odd
+    v[i] = a + b;
   }
 #pragma unroll
   for (int i = 0; i < 2; i++) {
-    const bool hi = lane & 4;
-    float keep = hi ? v[2 * i + 1] : v[2 * i];
-    float send = hi ? v[2 * i] : v[2 * i + 1];
-    v[i] = keep + __shfl_xor(send, 4);
+    const float a = dpp_move<ROW_SHL4, 0x5>(v[2 * i + 1], v[2 * i]);
+    const float b = dpp_move<ROW_SHR4, 0xA>(v[2 * i], v[2 * i + 1]);
+    v[i] = a + b;
   }
   {
     const bool hi = lane & 2;
     float keep = hi ? v[1] : v[0];
     float send = hi ? v[0] : v[1];
-    v[0] = keep + __shfl_xor(send, 2);
+    v[0] = keep + dpp_move<QUAD_XOR2, 0xF>(send, send);
   }
-  return v[0] + __shfl_xor(v[0], 1);
+  return v[0] + dpp_move<QUAD_XOR1, 0xF>(v[0], v[0]);
 }
 
 __device__ __forceinline__ int reduce32_index(int lane) {
   return ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1) | (((lane >> 3) & 1) << 2) |
          (((lane >> 2) & 1) << 3) | (((lane >> 1) & 1) << 4);
+}
+
+// test hook (droid_test_wave_reduce32): one wave, lane l reduces in[l][0..31]; out[l] = what wave_reduce32 returns in lane l
+__global__ __launch_bounds__(64) void wave_reduce32_test_kernel(const float* __restrict__ in, float* __restrict__ out) {
+  float v[32];
+#pragma unroll
+  for (int k = 0; k < 32; k++) v[k] = in[threadIdx.x * 32 + k];
+  out[threadIdx.x] = wave_reduce32(v);
+}
+void launch_wave_reduce32_test(const float* in, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(wave_reduce32_test_kernel, dim3(1), dim3(64), 0, s, in, out);
 }
 
 // Address of entry (gi, gj), gj <= gi, of the reduced camera system (row n = rhs) for the build kernels' atomics
@@ -420,13 +440,16 @@ __global__ __launch_bounds__(1024) void ba_prep_kernel(BaView vg, const int64_t*
 // EROWS (dense graphs): slots that the SYRK-only Schur kernel will serve also get their UNSCALED E rows
 // written to v.Ebuf (row 6*entry + n; the self row Ei = -sum_e Adj^T Eij is accumulated per pixel).
 // ZSPLIT: gridDim.z workgroups share a (slot, chunk), each taking a range of the slot's edges.
-template <bool DEPTH, bool EROWS, bool ZSPLIT>
+// FULL (host: HW % LIN_CP == 0): every pixel of every chunk exists, the per-lane `pix < HW` guards are compiled out; same
+// arithmetic, same bits.
+// The waves of a workgroup never meet inside the edge loop: each reduces its own 128 pixels and stores its own 32
+// words of Hpart (the assemble step adds the four), so a barrier is left only around the metadata (re)loads.
+template <bool DEPTH, bool EROWS, bool ZSPLIT, bool FULL>
 __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     BaView v, const float* __restrict__ poses, const float* __restrict__ disps,
     const float* __restrict__ intrinsics, const float* __restrict__ disps_sens,
     const float* __restrict__ targets, const float* __restrict__ weights,
     const float* __restrict__ eta, const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int zero_base) {
-  __shared__ float red[2][LIN_THREADS / 64][32];
   __shared__ SlotMetaT<double> sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int HW = v.HW, W = v.W;
@@ -499,8 +522,8 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     Cacc[p] = 0.f;
     wacc[p] = 0.f;
     disp[p] = 0.f;
-    if (DEPTH && pix[p] < HW) disp[p] = disps[(size_t)f * HW + pix[p]];
-    const int kk = pix[p] < HW ? pix[p] : 0;
+    if (DEPTH && (FULL || pix[p] < HW)) disp[p] = disps[(size_t)f * HW + pix[p]];
+    const int kk = (FULL || pix[p] < HW) ? pix[p] : 0;
     X0d[p] = ((double)(kk % W) - (double)K.cx) / (double)K.fx;
     X1d[p] = ((double)(kk / W) - (double)K.cy) / (double)K.fy;
   }
@@ -512,7 +535,7 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     const float* wg = weights + (size_t)e * 2 * HW;
 #pragma unroll
     for (int p = 0; p < LIN_PPT; p++) {
-      const bool ok = pix[p] < HW;
+      const bool ok = FULL || pix[p] < HW;
       const int k = ok ? pix[p] : 0;
       dst[p][0] = ok ? tg[k] : 0.f;
       dst[p][1] = ok ? tg[HW + k] : 0.f;
@@ -520,7 +543,6 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
       dst[p][3] = ok ? wg[HW + k] : 0.f;
     }
   };
-  int buf = 0;
   for (int x = xs; x < xend; x++) {
     if (DEPTH && (x == xs || ((x - xb) % SLOT_MAXE) == 0)) {  // (re)load the metadata chunk holding edge x
       if (x > xs) __syncthreads();
@@ -563,7 +585,10 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     for (int k = 0; k < 32; k++) acc[k] = 0.f;
 #pragma unroll
     for (int p = 0; p < LIN_PPT; p++) {
-      if (pix[p] < HW) {
+      // FULL: a wave-uniform test per pixel row of the chunk (always true there) instead of the per-lane guard.  It is
+      // not dropped altogether: with both pixels in one basic block the SLP vectoriser pairs them and the backend
+      // contracts other multiply-adds, which changes the rounding of Hpart, Q and w (profiles/lin_reduce_ab.txt)
+      if (FULL ? (chunk * LIN_CP + p * LIN_THREADS < HW) : (pix[p] < HW)) {
         const int k = pix[p];
         const float d = DEPTH ? disp[p] : disps[(size_t)ix * HW + k];
         const PixLin L = linearize_pixel_d(K, Rt, Rt + 9, X0d[p], X1d[p], d, in_cur[p][0], in_cur[p][1]);
@@ -608,24 +633,16 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
         }
       }
     }
-    // workgroup sum of the 27 block entries -> Hpart[e][chunk][0..31]
+    // wave sum of the 27 block entries -> Hpart[e][chunk][wave][0..31] (words 27..31: zeros; all 32 are written)
     const float tot = wave_reduce32(acc);
-    if ((lane & 1) == 0) red[buf][wave][reduce32_index(lane)] = tot;
-    __syncthreads();  // (s_waitcnt lgkmcnt(0); s_barrier on this target: the next edge's loads and this edge's stores stay in flight)
-    if (tid < 32) {
-      float s = 0.f;
-#pragma unroll
-      for (int wv_ = 0; wv_ < LIN_THREADS / 64; wv_++) s += red[buf][wv_][tid];
-      v.Hpart[((size_t)e * v.nch + chunk) * 32 + tid] = s;
-    }
-    buf ^= 1;  // double buffer: one barrier per edge
+    if ((lane & 1) == 0) v.Hpart[(((size_t)e * v.nch + chunk) * LIN_WAVES + wave) * 32 + reduce32_index(lane)] = tot;
   }
 
   if (DEPTH && ZSPLIT) {
     // partial sums of this edge range; ba_lin_finish_kernel adds them up in a fixed order
 #pragma unroll
     for (int p = 0; p < LIN_PPT; p++) {
-      if (pix[p] < HW) {
+      if (FULL || pix[p] < HW) {
         float* zp = v.zpart + (((size_t)blockIdx.z * v.M + m) * 8) * HW + pix[p];
         zp[0] = Cacc[p];
         zp[(size_t)HW] = wacc[p];
@@ -639,7 +656,7 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     const float alpha = 0.05f;  // dk:1396
 #pragma unroll
     for (int p = 0; p < LIN_PPT; p++) {
-      if (pix[p] < HW) {
+      if (FULL || pix[p] < HW) {
         const int k = pix[p];
         const size_t o = (size_t)m * HW + k;
         const float sens = disps_sens[(size_t)f * HW + k];
@@ -727,7 +744,13 @@ __device__ __forceinline__ void assemble_unit(const BaView& v, const float* __re
   if (!vi_ok && !vj_ok) return;
   if (t < 27) {
     double s = 0.0;
-    for (int c = 0; c < v.nch; c++) s += (double)v.Hpart[((size_t)e * v.nch + c) * 32 + t];
+    for (int c = 0; c < v.nch; c++) {  // per chunk the fp32 sum of its waves in wave order, then fp64 over the chunks
+      const float* hp = v.Hpart + ((size_t)e * v.nch + c) * LIN_WAVES * 32 + t;
+      float s32 = 0.f;
+#pragma unroll
+      for (int wv_ = 0; wv_ < LIN_WAVES; wv_++) s32 += hp[wv_ * 32];
+      s += (double)s32;
+    }
     if (t < 21) {
       int a = 0, rem = t;
       while (rem > a) {
@@ -2057,22 +2080,33 @@ void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStrea
   }
 }
 
+// the depth-slot linearisation for a graph: E rows for dense graphs, edge ranges when the slots alone do not fill the chip
+template <bool FULL>
+static auto lin_kernel_of(bool wide, bool zsplit) {
+  return wide ? (zsplit ? ba_lin_kernel<true, true, true, FULL> : ba_lin_kernel<true, true, false, FULL>)
+              : (zsplit ? ba_lin_kernel<true, false, true, FULL> : ba_lin_kernel<true, false, false, FULL>);
+}
+static auto lin_kernel_of(bool wide, bool zsplit, bool full) {
+  return full ? lin_kernel_of<true>(wide, zsplit) : lin_kernel_of<false>(wide, zsplit);
+}
+
 void launch_build_stage(const BaView& v, const BaLaunchPlan& plan, const float* poses, const float* disps,
                         const float* intr, const float* sens, const float* targets, const float* weights,
                         const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only,
                         int stage, hipStream_t s) {
   const bool depth = !motion_only && v.M > 0;
+  const bool full = v.HW % LIN_CP == 0;  // no ragged chunk: the linearisation without per-lane pixel guards
   switch (stage) {
     case 0:
       if (depth) {
         const dim3 g(v.M + plan.zero_wgs, v.nch, v.zsplit), b(LIN_THREADS);
-        const auto lin = v.wide ? (v.zsplit > 1 ? ba_lin_kernel<true, true, true> : ba_lin_kernel<true, true, false>)
-                                : (v.zsplit > 1 ? ba_lin_kernel<true, false, true> : ba_lin_kernel<true, false, false>);
+        const auto lin = lin_kernel_of(v.wide != 0, v.zsplit > 1, full);
         hipLaunchKernelGGL(lin, g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
         if (v.zsplit > 1)
           hipLaunchKernelGGL(ba_lin_finish_kernel, dim3(v.M, (v.HW + 255) / 256), dim3(256), 0, s, v, disps, sens, eta);
       } else if (v.E > 0) {
-        hipLaunchKernelGGL((ba_lin_kernel<false, false, false>), dim3(v.E + plan.zero_wgs, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
+        const auto lin = full ? ba_lin_kernel<false, false, false, true> : ba_lin_kernel<false, false, false, false>;
+        hipLaunchKernelGGL(lin, dim3(v.E + plan.zero_wgs, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
                            disps, intr, sens, targets, weights, eta, ii, jj, v.E);
       } else {
         if (v.packed) (void)hipMemsetAsync(v.psys, 0, sizeof(double) * pk_total(v.n), s);

@@ -288,6 +288,12 @@ int droid_ba_attach_status_mirror(const void *workspace, int *mirror);
  * The host never waits for the hint: not there yet = launch.  Results do not depend on it.  hints = NULL detaches. */
 int droid_ba_attach_launch_hints(const void *workspace, int *hints);
 
+/* The wave-level sum of the linearisation (exposed for tests): one 64-lane wave, lane l holding in[l][0..31], runs the
+ * halving butterfly (partners l^32, l^16, l^8, l^4, l^2, l^1); out[l] = the wave total of value
+ * bit5(l) + 2 bit4(l) + 4 bit3(l) + 8 bit2(l) + 16 bit1(l), in the bits that addition tree gives.
+ * in [64][32] f32, out [64] f32, device pointers. */
+int droid_test_wave_reduce32(const float *in, float *out, void *stream);
+
 /* Dense SPD solve used by the BA (exposed for tests): A [n,n] fp64 row-major (lower triangle
  * read, destroyed), b [n] fp64 -> x [n] fp64.  fail_flag (device int) is set to 1 when a pivot
  * is not positive.  scratch (128-byte aligned): >= droid_chol_scratch_doubles(n) doubles (the augmented system
