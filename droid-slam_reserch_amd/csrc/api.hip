@@ -56,6 +56,11 @@ void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask,
 size_t graph_mean_workspace_bytes(int E, int range);
 void launch_graph_mean(const void* src, const int64_t* index, void* out, int E, int64_t plane, int M, int range,
                        int compact, bool half, int* groups_out, void* workspace, hipStream_t s);
+// se3_ops.hip
+void launch_se3_unary(const float* in, float* out, int64_t n, int op, hipStream_t s);
+void launch_se3_mul(const float* a, int stride_a, const float* b, int stride_b, float* out, int64_t n, hipStream_t s);
+void launch_pose_interpolate(const float* poses, const float* tstamp, int N, const float* query, int M, float* out,
+                             int64_t* k0_out, int64_t* k1_out, hipStream_t s);
 // chol.hip
 void launch_chol_pack(const double* A, const double* b, double* S, int n, int ld, hipStream_t s);
 void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
@@ -753,6 +758,63 @@ int droid_proximity_edges(const float* dist, int ld, int bidirectional, int t, i
              known_ii, known_jj, n_known, edges_out, cap, count_out, workspace};
   launch_proximity_edges(a, (hipStream_t)stream);
   return check_hip("proximity_edges");
+}
+
+// ---- pose algebra (se3_ops.hip) ---------------------------------------------------------------------------------
+// [p, p + elems * 4 bytes) and [q, ...) share a byte.  Saturating: a record count near 2^58 times 64 bytes wraps.
+static bool f32_overlap(const void* p, uint64_t p_elems, const void* q, uint64_t q_elems, unsigned q_elem_bytes = 4) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  const uint64_t room_a = UINTPTR_MAX - a, room_b = UINTPTR_MAX - b;
+  const uintptr_t a1 = a + (p_elems > room_a / 4 ? room_a : p_elems * 4);
+  const uintptr_t b1 = b + (q_elems > room_b / q_elem_bytes ? room_b : q_elems * q_elem_bytes);
+  return p_elems > 0 && q_elems > 0 && a < b1 && b < a1;
+}
+
+int droid_se3_unary(const float* in, float* out, int64_t n, int op, void* stream) {
+  if (op < DROID_SE3_INV || op > DROID_SE3_MATRIX) return fail(DROID_E_ARG, "se3_unary: bad %s", "op (0 .. 3)");
+  if (n < 0) return fail(DROID_E_ARG, "se3_unary: bad %s", "n (negative)");
+  if (n > ((int64_t)1 << 62) / 16) return fail(DROID_E_ARG, "se3_unary: %s", "n * 16 exceeds the kernel's index range (2^62)");
+  if (n == 0) return DROID_OK;
+  if (!in || !out) return fail(DROID_E_ARG, "se3_unary: null %s", "pointer (in / out)");
+  const int win = op == DROID_SE3_EXP ? 6 : 7;
+  const int wout = op == DROID_SE3_LOG ? 6 : op == DROID_SE3_MATRIX ? 16 : 7;
+  if (!(op == DROID_SE3_INV && in == out) && f32_overlap(in, (uint64_t)n * win, out, (uint64_t)n * wout))
+    return fail(DROID_E_ARG, "se3_unary: %s", "out overlaps in (only INV may run in place, with out == in)");
+  launch_se3_unary(in, out, n, op, (hipStream_t)stream);
+  return check_hip("se3_unary");
+}
+
+int droid_se3_mul(const float* a, int stride_a, const float* b, int stride_b, float* out, int64_t n, void* stream) {
+  if (stride_a != 0 && stride_a != 7) return fail(DROID_E_ARG, "se3_mul: bad %s", "stride_a (0 or 7)");
+  if (stride_b != 0 && stride_b != 7) return fail(DROID_E_ARG, "se3_mul: bad %s", "stride_b (0 or 7)");
+  if (n < 0) return fail(DROID_E_ARG, "se3_mul: bad %s", "n (negative)");
+  if (n > ((int64_t)1 << 62) / 16) return fail(DROID_E_ARG, "se3_mul: %s", "n * 16 exceeds the kernel's index range (2^62)");
+  if (n == 0) return DROID_OK;
+  if (!a || !b || !out) return fail(DROID_E_ARG, "se3_mul: null %s", "pointer (a / b / out)");
+  if (!(stride_a == 7 && a == out) && f32_overlap(a, stride_a ? (uint64_t)n * 7 : 7, out, (uint64_t)n * 7))
+    return fail(DROID_E_ARG, "se3_mul: %s", "out overlaps a (allowed: out == a with stride_a = 7)");
+  if (!(stride_b == 7 && b == out) && f32_overlap(b, stride_b ? (uint64_t)n * 7 : 7, out, (uint64_t)n * 7))
+    return fail(DROID_E_ARG, "se3_mul: %s", "out overlaps b (allowed: out == b with stride_b = 7)");
+  launch_se3_mul(a, stride_a, b, stride_b, out, n, (hipStream_t)stream);
+  return check_hip("se3_mul");
+}
+
+int droid_pose_interpolate(const float* poses, const float* tstamp, int N, const float* query, int M, float* out,
+                           int64_t* k0_out, int64_t* k1_out, void* stream) {
+  if (N < 1) return fail(DROID_E_ARG, "pose_interpolate: bad %s", "N (at least 1)");
+  if (M < 0) return fail(DROID_E_ARG, "pose_interpolate: bad %s", "M (negative)");
+  if (M == 0) return DROID_OK;
+  if (!poses || !tstamp || !query || !out) return fail(DROID_E_ARG, "pose_interpolate: null %s", "pointer (poses / tstamp / query / out)");
+  const struct { const void* p; uint64_t elems; unsigned bytes; const char* name; } outs[3] = {
+      {out, (uint64_t)M * 7, 4, "out"}, {k0_out, (uint64_t)M, 8, "k0_out"}, {k1_out, (uint64_t)M, 8, "k1_out"}};
+  for (const auto& o : outs) {
+    if (!o.p) continue;
+    if (f32_overlap(poses, (uint64_t)N * 7, o.p, o.elems, o.bytes) || f32_overlap(tstamp, (uint64_t)N, o.p, o.elems, o.bytes) ||
+        f32_overlap(query, (uint64_t)M, o.p, o.elems, o.bytes))
+      return fail(DROID_E_ARG, "pose_interpolate: %s overlaps an input (poses / tstamp / query)", o.name);
+  }
+  launch_pose_interpolate(poses, tstamp, N, query, M, out, k0_out, k1_out, (hipStream_t)stream);
+  return check_hip("pose_interpolate");
 }
 
 }  // extern "C"

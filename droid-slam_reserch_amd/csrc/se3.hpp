@@ -309,4 +309,138 @@ __device__ __forceinline__ void retr_se3(const float* xi, const float* t, const 
   t1[0] += dt[0]; t1[1] += dt[1]; t1[2] += dt[2];
 }
 
+// ---- the pose algebra of the inference path (se3_ops.hip; contract: include/droid_backends_hip.h, "pose algebra") ----
+// Records tx ty tz qx qy qz qw, tangents tau phi, as above.  Everything below is evaluated in fp64 from the float32
+// record and rounded once by se3_store / the caller (the rule of rel_pose).  Quaternions are used as they are, never
+// renormalised: the rotation of a record is act_so3's expression, R = I + 2 w [v]x + 2 [v]x^2.
+struct Pose64 {
+  double t[3];
+  double q[4];
+};
+
+__device__ __forceinline__ Pose64 se3_load(const float* __restrict__ p) {
+  Pose64 a;
+  a.t[0] = p[0]; a.t[1] = p[1]; a.t[2] = p[2];
+  a.q[0] = p[3]; a.q[1] = p[4]; a.q[2] = p[5]; a.q[3] = p[6];
+  return a;
+}
+
+__device__ __forceinline__ void se3_store(const Pose64& a, float* p) {
+  p[0] = (float)a.t[0]; p[1] = (float)a.t[1]; p[2] = (float)a.t[2];
+  p[3] = (float)a.q[0]; p[4] = (float)a.q[1]; p[5] = (float)a.q[2]; p[6] = (float)a.q[3];
+}
+
+__device__ __forceinline__ void act_so3_d(const double* q, const double* X, double* Y) {  // act_so3 in double
+  const double uv0 = 2.0 * (q[1] * X[2] - q[2] * X[1]);
+  const double uv1 = 2.0 * (q[2] * X[0] - q[0] * X[2]);
+  const double uv2 = 2.0 * (q[0] * X[1] - q[1] * X[0]);
+  Y[0] = X[0] + q[3] * uv0 + (q[1] * uv2 - q[2] * uv1);
+  Y[1] = X[1] + q[3] * uv1 + (q[2] * uv0 - q[0] * uv2);
+  Y[2] = X[2] + q[3] * uv2 + (q[0] * uv1 - q[1] * uv0);
+}
+
+__device__ __forceinline__ void cross_d(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// q' = conj(q), t' = -(q' (*) t)
+__device__ __forceinline__ Pose64 se3_inv_d(const Pose64& a) {
+  Pose64 r;
+  r.q[0] = -a.q[0]; r.q[1] = -a.q[1]; r.q[2] = -a.q[2]; r.q[3] = a.q[3];
+  double y[3];
+  act_so3_d(r.q, a.t, y);
+  r.t[0] = -y[0]; r.t[1] = -y[1]; r.t[2] = -y[2];
+  return r;
+}
+
+// q = qa qb (Hamilton product in the ordering of retr_se3), t = ta + qa (*) tb
+__device__ __forceinline__ Pose64 se3_mul_d(const Pose64& a, const Pose64& b) {
+  Pose64 r;
+  r.q[0] = a.q[3] * b.q[0] + a.q[0] * b.q[3] + a.q[1] * b.q[2] - a.q[2] * b.q[1];
+  r.q[1] = a.q[3] * b.q[1] + a.q[1] * b.q[3] + a.q[2] * b.q[0] - a.q[0] * b.q[2];
+  r.q[2] = a.q[3] * b.q[2] + a.q[2] * b.q[3] + a.q[0] * b.q[1] - a.q[1] * b.q[0];
+  r.q[3] = a.q[3] * b.q[3] - a.q[0] * b.q[0] - a.q[1] * b.q[1] - a.q[2] * b.q[2];
+  double y[3];
+  act_so3_d(a.q, b.t, y);
+  r.t[0] = a.t[0] + y[0]; r.t[1] = a.t[1] + y[1]; r.t[2] = a.t[2] + y[2];
+  return r;
+}
+
+// 4x4 row-major: R entry by entry as rel_pose_mat writes it, t in the fourth column, last row 0 0 0 1
+__device__ __forceinline__ void se3_matrix_d(const Pose64& a, double* M) {
+  const double x = a.q[0], y = a.q[1], z = a.q[2], w = a.q[3];
+  M[0] = 1.0 - 2.0 * (y * y + z * z); M[1] = 2.0 * (x * y - z * w);       M[2] = 2.0 * (x * z + y * w);        M[3] = a.t[0];
+  M[4] = 2.0 * (x * y + z * w);       M[5] = 1.0 - 2.0 * (x * x + z * z); M[6] = 2.0 * (y * z - x * w);        M[7] = a.t[1];
+  M[8] = 2.0 * (x * z - y * w);       M[9] = 2.0 * (y * z + x * w);       M[10] = 1.0 - 2.0 * (x * x + y * y); M[11] = a.t[2];
+  M[12] = 0.0; M[13] = 0.0; M[14] = 0.0; M[15] = 1.0;
+}
+
+// Below these squared angles the closed forms give way to their Taylor series ("pose algebra": in fp64 the
+// closed forms lose nothing that matters down to theta ~ 1e-7; the series are there for theta = 0 and its neighbourhood,
+// and the thresholds sit where the first dropped term is below 1e-22 of the kept ones).
+#define DROID_SE3_SERIES_Q 1e-8    // sin(theta/2)/theta             : theta^6 / 645120 dropped
+#define DROID_SE3_SERIES_V 1e-4    // coefficients of V and V^-1     : theta^8 terms dropped
+#define DROID_SE3_SERIES_LOG 1e-10 // atan(n/w)/n, against (n/w)^2   : (n/w)^4 / 5 dropped
+
+// exp: q = (sin(theta/2)/theta phi, cos(theta/2)), t = V tau,
+// V = I + (1 - cos theta)/theta^2 [phi]x + (theta - sin theta)/theta^3 [phi]x^2; 1 - cos theta as 2 sin^2(theta/2)
+__device__ __forceinline__ Pose64 se3_exp_d(const double* xi) {
+  const double* tau = xi;
+  const double* phi = xi + 3;
+  const double th2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+  const double th = sqrt(th2);
+  const double s = sin(0.5 * th), c = cos(0.5 * th);
+  const double imag = th2 < DROID_SE3_SERIES_Q ? 0.5 - th2 * (1.0 / 48.0) + th2 * th2 * (1.0 / 3840.0) : s / th;
+  double a, b;
+  if (th2 < DROID_SE3_SERIES_V) {
+    a = 0.5 - th2 * (1.0 / 24.0 - th2 * (1.0 / 720.0 - th2 * (1.0 / 40320.0)));
+    b = 1.0 / 6.0 - th2 * (1.0 / 120.0 - th2 * (1.0 / 5040.0 - th2 * (1.0 / 362880.0)));
+  } else {
+    a = 2.0 * s * s / th2;
+    b = (th - 2.0 * s * c) / (th * th2);
+  }
+  Pose64 r;
+  r.q[0] = imag * phi[0]; r.q[1] = imag * phi[1]; r.q[2] = imag * phi[2]; r.q[3] = c;
+  double u[3], v[3];
+  cross_d(phi, tau, u);
+  cross_d(phi, u, v);
+  r.t[0] = tau[0] + a * u[0] + b * v[0];
+  r.t[1] = tau[1] + a * u[1] + b * v[1];
+  r.t[2] = tau[2] + a * u[2] + b * v[2];
+  return r;
+}
+
+// log: phi = 2 atan(n/w)/n v, n = |v| (the rotation vector of least norm; log(c q) = log(q) for every c != 0, since
+// only n/w and v/n enter), +pi v/n at w == 0; tau = V^-1 t, V^-1 = I - 1/2 [phi]x + c [phi]x^2,
+// c = (1 - theta cos(theta/2) / (2 sin(theta/2))) / theta^2 with cos(theta/2) / sin(theta/2) = |w| / n.
+__device__ __forceinline__ void se3_log_d(const Pose64& a, double* xi) {
+  const double* v = a.q;
+  const double w = a.q[3];
+  const double n2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+  const double n = sqrt(n2);
+  double f;
+  if (w == 0.0)
+    f = 3.14159265358979323846 / n;
+  else if (n2 < DROID_SE3_SERIES_LOG * (w * w))
+    f = 2.0 / w - (2.0 / 3.0) * n2 / (w * w * w);
+  else
+    f = 2.0 * atan(n / w) / n;
+  double* phi = xi + 3;
+  phi[0] = f * v[0]; phi[1] = f * v[1]; phi[2] = f * v[2];
+  const double th2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2];
+  double c;
+  if (th2 < DROID_SE3_SERIES_V)
+    c = 1.0 / 12.0 + th2 * (1.0 / 720.0 + th2 * (1.0 / 30240.0 + th2 * (1.0 / 1209600.0)));
+  else
+    c = (1.0 - 0.5 * sqrt(th2) * (fabs(w) / n)) / th2;
+  double u[3], y[3];
+  cross_d(phi, a.t, u);
+  cross_d(phi, u, y);
+  xi[0] = a.t[0] - 0.5 * u[0] + c * y[0];
+  xi[1] = a.t[1] - 0.5 * u[1] + c * y[1];
+  xi[2] = a.t[2] - 0.5 * u[2] + c * y[2];
+}
+
 }  // namespace droid

@@ -17,6 +17,9 @@ import torch
 from . import _lib
 from ._lib import DroidBackendError  # noqa: F401
 from .ba_binding import BAProblemDev, BaBinding, read_status
+from . import se3
+from .se3 import SE3
+from .se3 import interpolate as pose_interpolate
 
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
            "altcorr_backward", "corr_index_forward", "corr_index_backward",
@@ -25,7 +28,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "proximity_edges",       # add_proximity_factors' edge selection, on the device
            "corr_volume_pyramid",   # CorrBlock.__init__ for a list of edges, in one launch
            "upsample_disps", "cvx_upsample",   # DepthVideo.upsample / droid_net.cvx_upsample, in one launch
-           "graph_mean", "scatter_mean"]       # GraphAgg's source-frame mean (torch_scatter.scatter_mean), no atomics
+           "graph_mean", "scatter_mean",       # GraphAgg's source-frame mean (torch_scatter.scatter_mean), no atomics
+           "SE3", "pose_interpolate"]          # the pose algebra of the inference path without lietorch (droid_backends.se3)
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}

@@ -465,6 +465,60 @@ int droid_proximity_edges(const float *dist, int ld, int bidirectional, int t, i
                           int64_t *edges_out, int cap, int *count_out, void *workspace, size_t workspace_bytes,
                           void *stream);
 
+/* ------------------------------------------------------------------ pose algebra */
+
+/* The SE3 group operations the inference path takes from lietorch -- `PoseTrajectoryFiller.__fill`
+ * (droid_slam/trajectory_filler.py:43-58), the visualiser's `SE3(poses).inv().matrix()`, `Droid.terminate`'s final
+ * `.inv()`, the multi-session `T.inv() * poses` -- on [n,7] pose records.  Not among the reference's nine operators.
+ * None of them acts on points (reproject / iproj own the point actions), none has a gradient.
+ * Records are tx ty tz qx qy qz qw, tangents tau_x tau_y tau_z phi_x phi_y phi_z.  Quaternions are used as they are and
+ * never renormalised: the rotation of a record is R = I + 2 w [v]x + 2 [v]x^2 whatever its norm.
+ * Arithmetic: every value is evaluated in fp64 from the float32 inputs and rounded to float32 once.  Per component
+ *   |out - exact| <= 2^-23 |exact| + 2^-36 S,  S = 1 + the largest |translation component| among inputs and result
+ * ("pose algebra").  Parity with lietorch itself is unpinned: it cannot be built for this device, so the
+ * yardstick is the fp64 restatement of the formulas below (tests/se3_ref.py), not lietorch's own series thresholds.
+ *  INV     q' = conj(q), t' = -(q' (*) t)                     ((*): the rotation above)
+ *  MATRIX  row-major 4x4, R entry by entry, t in the fourth column, last row 0 0 0 1
+ *  EXP     q = (sin(theta/2)/theta phi, cos(theta/2)), t = V tau,
+ *          V = I + (1 - cos theta)/theta^2 [phi]x + (theta - sin theta)/theta^3 [phi]x^2; continuous through theta = 0
+ *  LOG     phi = 2 atan(n/w)/n v with n = |v|: the rotation vector of least norm, |phi| <= pi; 2/w - (2/3) n^2/w^3 as
+ *          n -> 0; +pi v/n when w == 0; log(c q) = log(q) for every c != 0, negative c included (at exactly w == 0
+ *          the least-norm vector is not unique, and the + follows the sign of v: -q gives -phi, the same rotation).
+ *          tau = V^-1 t, V^-1 = I - 1/2 [phi]x + c [phi]x^2, c = (1 - theta cos(theta/2) / (2 sin(theta/2))) / theta^2.
+ *  mul     out[k] = a[k] * b[k]: q = qa qb (Hamilton product), t = ta + qa (*) tb.  stride_a, stride_b are 7, or 0 to
+ *          broadcast one record.
+ * Each thread reads its records before it writes: out == in is allowed for INV, out == a or out == b for mul where that
+ * side's stride is 7.  Any other overlap of out with an input is refused.
+ * Refused with DROID_E_ARG and a message naming the function and the argument, before any HIP call: op outside 0 .. 3;
+ * n < 0; n * 16 beyond 2^62; a stride other than 0 or 7; a null pointer with n > 0; an overlap as above.  n == 0 launches
+ * nothing and returns 0. */
+#define DROID_SE3_INV 0     /* in [n,7] -> out [n,7]  */
+#define DROID_SE3_LOG 1     /* in [n,7] -> out [n,6]  (tau, phi) */
+#define DROID_SE3_EXP 2     /* in [n,6] -> out [n,7]  */
+#define DROID_SE3_MATRIX 3  /* in [n,7] -> out [n,16] row-major 4x4, last row 0 0 0 1 */
+int droid_se3_unary(const float *in, float *out, int64_t n, int op, void *stream);
+int droid_se3_mul(const float *a, int stride_a, const float *b, int stride_b, float *out, int64_t n, void *stream);
+
+/* The linear pose interpolation of `PoseTrajectoryFiller.__fill` (trajectory_filler.py:44-58) in one launch, without
+ * the reference's one blocking read per query.  poses [>= N,7], tstamp [>= N], query [M] float32 on the device (the
+ * reference compares a Python number with a float32 tensor, so a float32 query reproduces it).  For the query t:
+ *   k0 = max(#{k < N : tstamp[k] <= t} - 1, 0)      a count, as in the reference: nothing assumes sorted stamps
+ *   k1 = k0 + 1 if k0 < N - 1 else k0
+ *   dt = tstamp[k1] - tstamp[k0] + 1e-3
+ *   out = exp( log(P[k1] P[k0]^-1) / dt * (t - tstamp[k0]) ) P[k0]
+ * all in fp64 (the two stamp differences included), rounded once; the bound above holds with S multiplied by
+ * 1 + |t - tstamp[k0]| / dt.  out [M,7]; k0_out, k1_out [M] int64 (either may be NULL) receive the brackets: the `ii`
+ * of the edges the filler adds next.  Nothing outside [0, N) is read.
+ * Where this differs from the reference: for t before every stamp the reference computes k0 = -1, which wraps to the
+ * last keyframe and then goes into `ba` as a frame index.  Here k0 clamps to 0 and the pose is extrapolated backwards
+ * from the first bracket.
+ * After the last stamp k1 == k0: the relative pose is the exact identity and out = P[k0].  A NaN stamp is never
+ * counted.  A NaN query gives k0 = 0 and NaN poses.
+ * Refused with DROID_E_ARG before any HIP call: N < 1; M < 0; a null poses / tstamp / query / out with M > 0; out, k0_out
+ * or k1_out overlapping an input.  M == 0 launches nothing and returns 0. */
+int droid_pose_interpolate(const float *poses, const float *tstamp, int N, const float *query, int M,
+                           float *out /*[M,7]*/, int64_t *k0_out /*[M]*/, int64_t *k1_out /*[M]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
