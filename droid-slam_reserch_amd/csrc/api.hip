@@ -61,6 +61,12 @@ void launch_se3_unary(const float* in, float* out, int64_t n, int op, hipStream_
 void launch_se3_mul(const float* a, int stride_a, const float* b, int stride_b, float* out, int64_t n, hipStream_t s);
 void launch_pose_interpolate(const float* poses, const float* tstamp, int N, const float* query, int M, float* out,
                              int64_t* k0_out, int64_t* k1_out, hipStream_t s);
+// point_cloud.hip
+size_t point_cloud_workspace_bytes(int n, int H, int W);
+void launch_point_cloud(const float* poses, const float* disps, const float* intr, const int64_t* index,
+                        const float* thresh, const uint8_t* images, int n, int nbuf, int H, int W, int min_count,
+                        double disp_ratio, float* points, float* colors, int* src, int* offsets, float* matrices,
+                        void* workspace, hipStream_t s);
 // chol.hip
 void launch_chol_pack(const double* A, const double* b, double* S, int n, int ld, hipStream_t s);
 void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
@@ -815,6 +821,63 @@ int droid_pose_interpolate(const float* poses, const float* tstamp, int N, const
   }
   launch_pose_interpolate(poses, tstamp, N, query, M, out, k0_out, k1_out, (hipStream_t)stream);
   return check_hip("pose_interpolate");
+}
+
+// ---- point cloud (point_cloud.hip) ------------------------------------------------------------------------------
+// sizes droid_point_cloud and its workspace query check; <0 after fail()
+static int point_cloud_check(int n, int H, int W) {
+  if (n < 0) return fail(DROID_E_ARG, "point_cloud: bad %s", "n (negative)");
+  if (H < 1 || W < 1) return fail(DROID_E_ARG, "point_cloud: bad %s", "map size (H, W >= 1)");
+  if ((unsigned __int128)(n > 0 ? n : 1) * (unsigned)H * (unsigned)W >= ((unsigned __int128)1 << 31))
+    return fail(DROID_E_ARG, "point_cloud: %s", "n * H * W reaches 2^31 (rows and offsets are 32-bit)");
+  return 0;
+}
+
+size_t droid_point_cloud_workspace_bytes(int n, int H, int W) {
+  if (point_cloud_check(n, H, W)) return 0;
+  return point_cloud_workspace_bytes(n, H, W);
+}
+
+int droid_point_cloud(const float* poses, const float* disps, const float* intrinsics, const int64_t* index,
+                      const float* thresh, const uint8_t* images, int n, int nbuf, int H, int W, int min_count,
+                      double disp_ratio, float* points, float* colors, int* src, int* offsets, float* matrices,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = point_cloud_check(n, H, W);
+  if (rc) return rc;
+  if (nbuf < 1) return fail(DROID_E_ARG, "point_cloud: bad %s", "nbuf (at least 1)");
+  if (n == 0) return DROID_OK;
+  if (!poses || !disps || !intrinsics || !index || !thresh)
+    return fail(DROID_E_ARG, "point_cloud: null %s", "pointer (poses / disps / intrinsics / index / thresh)");
+  if (!points || !src || !offsets || !matrices)
+    return fail(DROID_E_ARG, "point_cloud: null %s", "pointer (points / src / offsets / matrices)");
+  if ((images == nullptr) != (colors == nullptr))
+    return fail(DROID_E_ARG, "point_cloud: %s", "images and colors go together (both or neither)");
+  if (!workspace) return fail(DROID_E_ARG, "point_cloud: null %s", "workspace");
+  if (workspace_bytes < point_cloud_workspace_bytes(n, H, W)) return fail(DROID_E_ARG, "point_cloud: %s", "workspace too small");
+  if ((uintptr_t)workspace % 8 != 0) return fail(DROID_E_ARG, "point_cloud: %s", "workspace is not 8-byte aligned");
+  const uint64_t hw = (uint64_t)H * W, cap = (uint64_t)n * hw;
+  struct Range { const void* p; uint64_t bytes; const char* name; };
+  const Range ins[6] = {{poses, (uint64_t)nbuf * 28, "poses"}, {disps, (uint64_t)nbuf * hw * 4, "disps"},
+                        {intrinsics, 16, "intrinsics"}, {index, (uint64_t)n * 8, "index"}, {thresh, (uint64_t)n * 4, "thresh"},
+                        {images, images ? (uint64_t)nbuf * 192 * hw : 0, "images"}};
+  const Range outs[6] = {{points, cap * 12, "points"}, {colors, colors ? cap * 12 : 0, "colors"}, {src, cap * 4, "src"},
+                         {offsets, ((uint64_t)n + 1) * 4, "offsets"}, {matrices, (uint64_t)n * 64, "matrices"},
+                         {workspace, point_cloud_workspace_bytes(n, H, W), "workspace"}};
+  auto overlap = [](const Range& a, const Range& b) {   // share a byte; an end beyond the address space saturates
+    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
+    const uintptr_t a1 = a0 + (a.bytes > UINTPTR_MAX - a0 ? UINTPTR_MAX - a0 : a.bytes);
+    const uintptr_t b1 = b0 + (b.bytes > UINTPTR_MAX - b0 ? UINTPTR_MAX - b0 : b.bytes);
+    return a.bytes > 0 && b.bytes > 0 && a0 < b1 && b0 < a1;
+  };
+  for (int o = 0; o < 6; o++) {
+    for (const Range& in : ins)
+      if (overlap(outs[o], in)) return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", outs[o].name, in.name);
+    for (int q = 0; q < o; q++)
+      if (overlap(outs[o], outs[q])) return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", outs[o].name, outs[q].name);
+  }
+  launch_point_cloud(poses, disps, intrinsics, index, thresh, images, n, nbuf, H, W, min_count, disp_ratio, points, colors,
+                     src, offsets, matrices, workspace, (hipStream_t)stream);
+  return check_hip("point_cloud");
 }
 
 }  // extern "C"

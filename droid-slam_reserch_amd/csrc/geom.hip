@@ -274,32 +274,8 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(
   const int64_t i64 = inds[b];  // checked before it is narrowed: 2^32 + 3 is not frame 3
   float cnt = 0.f;
   if (i64 >= 0 && i64 < nbuf) {
-    const int ix = (int)i64;
     const Intr K = {intrinsics[0], intrinsics[1], intrinsics[2], intrinsics[3]};
-    const float t = thresh[b];
-    const float ui = (float)(k % W), vi = (float)(k / W);
-    const float di = disps[(size_t)ix * HW + k];
-    for (int nb = 0; nb < 6; nb++) {
-      const int jx = (nb < 3) ? ix - nb - 1 : ix + nb;  // dk:695
-      if (jx < 0 || jx >= nbuf) continue;
-      const Rel T = rel_pose_plain(poses, ix, jx);
-      float Xj[4];
-      transform_pixel(K, T, ui, vi, di, Xj);
-      const float uj = K.fx * (Xj[0] / Xj[2]) + K.cx;
-      const float vj = K.fy * (Xj[1] / Xj[2]) + K.cy;
-      const float dj = Xj[3] / Xj[2];
-      const int u0 = (int)floorf(uj), v0 = (int)floorf(vj);
-      if (u0 >= 0 && v0 >= 0 && u0 < W - 1 && v0 < H - 1) {
-        const float* dp = disps + (size_t)jx * HW;
-        const float d00 = dp[(v0 + 0) * W + u0 + 0], d01 = dp[(v0 + 0) * W + u0 + 1];
-        const float d10 = dp[(v0 + 1) * W + u0 + 0], d11 = dp[(v0 + 1) * W + u0 + 1];
-        const float idj = 1.0f / dj;
-        if (fabsf(idj - 1.0f / d00) < t) cnt += 1.f;
-        else if (fabsf(idj - 1.0f / d01) < t) cnt += 1.f;
-        else if (fabsf(idj - 1.0f / d10) < t) cnt += 1.f;
-        else if (fabsf(idj - 1.0f / d11) < t) cnt += 1.f;
-      }
-    }
+    cnt = depth_filter_count(poses, disps, K, (int)i64, thresh[b], k, nbuf, H, W);
   }
   counter[(size_t)b * HW + k] = cnt;
 }

@@ -154,6 +154,39 @@ __device__ __forceinline__ void transform_pixel(const Intr& K, const Rel& T, flo
   Xj[2] += disp * T.t[2];
 }
 
+// The per-pixel body of depth_filter_kernel (dk:661-775), shared by depth_filter (geom.hip) and point_cloud
+// (point_cloud.hip): of the six temporal neighbours of frame ix inside [0, nbuf), the number whose depth agrees with
+// pixel k of frame ix within t.  ix is inside the buffer (the callers test the int64 index before they narrow it).
+__device__ __forceinline__ float depth_filter_count(const float* __restrict__ poses, const float* __restrict__ disps,
+                                                    const Intr& K, int ix, float t, int k, int nbuf, int H, int W) {
+  const int HW = H * W;
+  float cnt = 0.f;
+  const float ui = (float)(k % W), vi = (float)(k / W);
+  const float di = disps[(size_t)ix * HW + k];
+  for (int nb = 0; nb < 6; nb++) {
+    const int jx = (nb < 3) ? ix - nb - 1 : ix + nb;  // dk:695
+    if (jx < 0 || jx >= nbuf) continue;
+    const Rel T = rel_pose_plain(poses, ix, jx);
+    float Xj[4];
+    transform_pixel(K, T, ui, vi, di, Xj);
+    const float uj = K.fx * (Xj[0] / Xj[2]) + K.cx;
+    const float vj = K.fy * (Xj[1] / Xj[2]) + K.cy;
+    const float dj = Xj[3] / Xj[2];
+    const int u0 = (int)floorf(uj), v0 = (int)floorf(vj);
+    if (u0 >= 0 && v0 >= 0 && u0 < W - 1 && v0 < H - 1) {
+      const float* dp = disps + (size_t)jx * HW;
+      const float d00 = dp[(v0 + 0) * W + u0 + 0], d01 = dp[(v0 + 0) * W + u0 + 1];
+      const float d10 = dp[(v0 + 1) * W + u0 + 0], d11 = dp[(v0 + 1) * W + u0 + 1];
+      const float idj = 1.0f / dj;
+      if (fabsf(idj - 1.0f / d00) < t) cnt += 1.f;
+      else if (fabsf(idj - 1.0f / d01) < t) cnt += 1.f;
+      else if (fabsf(idj - 1.0f / d10) < t) cnt += 1.f;
+      else if (fabsf(idj - 1.0f / d11) < t) cnt += 1.f;
+    }
+  }
+  return cnt;
+}
+
 // Per-pixel linearisation of one edge: both residual rows.  Jj rows have a structural zero each
 // (Jj_u[1] = 0, Jj_v[0] = 0; dk:313, :345).
 struct PixLin {

@@ -29,7 +29,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "corr_volume_pyramid",   # CorrBlock.__init__ for a list of edges, in one launch
            "upsample_disps", "cvx_upsample",   # DepthVideo.upsample / droid_net.cvx_upsample, in one launch
            "graph_mean", "scatter_mean",       # GraphAgg's source-frame mean (torch_scatter.scatter_mean), no atomics
-           "SE3", "pose_interpolate"]          # the pose algebra of the inference path without lietorch (droid_backends.se3)
+           "SE3", "pose_interpolate",          # the pose algebra of the inference path without lietorch (droid_backends.se3)
+           "point_cloud", "PointCloud"]        # the viewers' filtered, coloured map of dirty keyframes, compacted on the device
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}
@@ -347,6 +348,108 @@ def iproj(poses, disps, intrinsics):
     _lib.check(lib.droid_iproj(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), nm, H, W,
                                points.data_ptr(), _stream()), "iproj")
     return points
+
+
+_pc_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of point_cloud
+
+
+class PointCloud:
+    """What `point_cloud` returns: points [P,3] float32, colors [P,3] float32 or None, src [P] int32 (pixel v * w + u),
+    offsets [n+1] int32 on the device (selection b owns rows offsets[b]:offsets[b+1]), matrices [n,4,4] float32, and
+    offsets_host, the same offsets as a list of ints (None with sync=False, where the tensors keep their capacity
+    n * h * w and rows from offsets[n] on are unwritten)."""
+    __slots__ = ("points", "colors", "src", "offsets", "matrices", "offsets_host")
+
+    def __init__(self, points, colors, src, offsets, matrices, offsets_host):
+        self.points, self.colors, self.src = points, colors, src
+        self.offsets, self.matrices, self.offsets_host = offsets, matrices, offsets_host
+
+    def __len__(self):
+        if self.offsets_host is None:
+            raise TypeError("len() of a point cloud that was not synchronised (sync=False): read offsets[-1]")
+        return self.offsets_host[-1]
+
+
+def point_cloud(poses, disps, intrinsics, index, thresh, images=None, min_count=2, disp_ratio=0.5, sync=True):
+    """The filtered, coloured point cloud of the keyframes `index` -- the body of the reference fork's viewers
+    (visualization.py:100-142: SE3(poses).inv(), iproj, depth_filter, `(count >= 2) & (disps > .5 * mean)`, the colour
+    lookup `images[:, [2,1,0], 3::8, 3::8] / 255.0` and the per-frame boolean indexing) in one call, with nothing per
+    pixel on the host.  poses [nbuf,7], disps [nbuf,h,w], intrinsics [4] float32; index [n] int64 on the device (never
+    read by the host; an entry outside the buffer yields no point and a zero matrix); thresh a Python float or an [n]
+    float32 tensor, one per selection; images [nbuf,3,8h,8w] uint8 (BGR, as `video.images`) or None.  Returns a
+    `PointCloud`: the points in the order of index, row-major within a frame.  sync=True reads offsets (n + 1
+    integers, the one synchronisation) and trims points / colors / src to the P points kept; sync=False reads nothing
+    and returns the capacity tensors [n * h * w, ...].  Contract: include/droid_backends_hip.h (droid_point_cloud).
+    No autograd.  An addition."""
+    lib = _lib.load()
+    what = "point_cloud"
+    tensors = [(poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (index, "index")]
+    if isinstance(thresh, torch.Tensor):
+        tensors.append((thresh, "thresh"))
+    if images is not None:
+        tensors.append((images, "images"))
+    for x, name in tensors:
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{what}: {name} must be a tensor, got {type(x).__name__}")
+    for x, name in tensors:
+        want = torch.int64 if name == "index" else torch.uint8 if name == "images" else torch.float32
+        if x.dtype != want:
+            raise RuntimeError(f"{what}: {name} must be {str(want).replace('torch.', '')}, got {x.dtype}")
+    if poses.dim() != 2 or poses.shape[1] != 7 or disps.dim() != 3 or intrinsics.dim() != 1 or intrinsics.shape[0] != 4:
+        raise RuntimeError(f"{what}: poses must be [nbuf, 7], disps [nbuf, h, w], intrinsics [4], got "
+                           f"{tuple(poses.shape)}, {tuple(disps.shape)}, {tuple(intrinsics.shape)}")
+    if index.dim() != 1:
+        raise RuntimeError(f"{what}: index must be [n], got {tuple(index.shape)}")
+    n = int(index.shape[0])
+    nbuf, h, w = (int(v) for v in disps.shape)
+    if isinstance(thresh, torch.Tensor) and tuple(thresh.shape) != (n,):
+        raise RuntimeError(f"{what}: thresh must be a number or [n] = [{n}], one per selection, got {tuple(thresh.shape)}")
+    if images is not None and tuple(images.shape) != (nbuf, 3, 8 * h, 8 * w):
+        raise RuntimeError(f"{what}: images must be [{nbuf}, 3, {8 * h}, {8 * w}] for {nbuf} frames of {h} x {w}, got "
+                           f"{tuple(images.shape)}")
+    for x, name in tensors:
+        if not x.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be contiguous")
+    for x, name in tensors:
+        if not x.is_cuda:
+            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
+        if x.device != disps.device:
+            raise RuntimeError(f"{what}: {name} is on {x.device}, disps on {disps.device}")
+    if h < 1 or w < 1:
+        raise RuntimeError(f"{what}: disps must have h, w >= 1, got {tuple(disps.shape)}")
+    if n * h * w >= 2 ** 31:
+        raise RuntimeError(f"{what}: n * h * w = {n * h * w} reaches 2^31 (rows and offsets are 32-bit): select in parts")
+    dev = disps.device
+    nbuf = min(nbuf, int(poses.shape[0]))
+    with torch.cuda.device(dev):
+        if not isinstance(thresh, torch.Tensor):
+            thresh = torch.full((n,), float(thresh), dtype=torch.float32, device=dev)
+        cap = n * h * w
+        points = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+        colors = torch.empty((cap, 3), dtype=torch.float32, device=dev) if images is not None else None
+        src = torch.empty((cap,), dtype=torch.int32, device=dev)
+        matrices = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
+        if n == 0 or nbuf == 0:   # nothing selected (or nothing to select from): no launch
+            offsets = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
+            matrices.zero_()
+            return PointCloud(points[:0], None if colors is None else colors[:0], src[:0], offsets, matrices,
+                              [0] * (n + 1) if sync else None)
+        offsets = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+        stream = _stream()
+        nbytes = lib.droid_point_cloud_workspace_bytes(n, h, w)
+        key = (dev.index, stream)
+        ws = _pc_ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = _pc_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+        _lib.check(lib.droid_point_cloud(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), index.data_ptr(),
+                                         thresh.data_ptr(), _ptr(images), n, nbuf, h, w, int(min_count), float(disp_ratio),
+                                         points.data_ptr(), _ptr(colors), src.data_ptr(), offsets.data_ptr(),
+                                         matrices.data_ptr(), ws.data_ptr(), ws.numel(), stream), what)
+        if not sync:
+            return PointCloud(points, colors, src, offsets, matrices, None)
+        host = offsets.tolist()   # the one synchronisation: n + 1 integers
+    P = host[-1]
+    return PointCloud(points[:P], None if colors is None else colors[:P], src[:P], offsets, matrices, host)
 
 
 def _upsample_args(what, mask, n, h, w, f32, ix=None):

@@ -29,6 +29,7 @@ SYMBOLS = [
     "droid_cvx_upsample",
     "droid_graph_mean_workspace_bytes", "droid_graph_mean",
     "droid_se3_unary", "droid_se3_mul", "droid_pose_interpolate",
+    "droid_point_cloud_workspace_bytes", "droid_point_cloud",
     "droid_test_wave_reduce32",
 ]
 
@@ -111,10 +112,14 @@ def load() -> ctypes.CDLL:
     lib.droid_se3_unary.argtypes = [vp, vp, ctypes.c_int64, c_int, vp]
     lib.droid_se3_mul.argtypes = [vp, c_int, vp, c_int, vp, ctypes.c_int64, vp]
     lib.droid_pose_interpolate.argtypes = [vp, vp, c_int, vp, c_int, vp, vp, vp, vp]
+    lib.droid_point_cloud_workspace_bytes.argtypes = [c_int] * 3
+    lib.droid_point_cloud_workspace_bytes.restype = sz
+    lib.droid_point_cloud.argtypes = [vp] * 6 + [c_int] * 5 + [ctypes.c_double] + [vp] * 6 + [sz, vp]
     lib.droid_test_wave_reduce32.argtypes = [vp, vp, vp]
     for s in SYMBOLS[2:]:
         if s not in ("droid_ba_workspace_bytes", "droid_ba_system", "droid_ba_packed_system", "droid_chol_scratch_doubles",
-                     "droid_proximity_workspace_bytes", "droid_graph_mean_workspace_bytes"):
+                     "droid_proximity_workspace_bytes", "droid_graph_mean_workspace_bytes",
+                     "droid_point_cloud_workspace_bytes"):
             getattr(lib, s).restype = c_int
     if lib.droid_abi_version() != 1:
         raise DroidBackendError("ABI version mismatch")

@@ -519,6 +519,55 @@ int droid_se3_mul(const float *a, int stride_a, const float *b, int stride_b, fl
 int droid_pose_interpolate(const float *poses, const float *tstamp, int N, const float *query, int M,
                            float *out /*[M,7]*/, int64_t *k0_out /*[M]*/, int64_t *k1_out /*[M]*/, void *stream);
 
+/* ------------------------------------------------------------------ point cloud */
+
+/* The filtered, coloured point cloud of selected keyframes -- the body of the reference fork's viewers and map tools
+ * (visualization.py:100-142: index_select, SE3(poses).inv(), iproj, depth_filter, the count / disparity mask, the
+ * per-frame boolean indexing on the host) -- selection, filtering, colouring and ordered compaction on the stream, with
+ * nothing per pixel on the host.  Not one of the reference's nine operators.
+ *
+ * Inputs, all on one device, all contiguous, only read:
+ *   poses [nbuf,7] float32, world-to-camera, as stored ;  disps [nbuf,H,W] float32 ;  intrinsics [4] float32 ;
+ *   index [n] int64 (the host never reads it) ;  thresh [n] float32, one per selection ;
+ *   images [nbuf,3,8H,8W] uint8, stored BGR as in `video.images`, or NULL (then colors is NULL too) ;
+ *   min_count (the reference uses 2) ;  disp_ratio (the reference uses 0.5).
+ * Per selection b with i = index[b].  i outside [0,nbuf), tested as an int64 before any narrowing: the selection yields
+ * no point and an all-zero matrix.  Otherwise:
+ *  1. Pose inverse.  G = inv(poses[i]) by the pose algebra's contract above: fp64 from the float32 record, the
+ *     quaternion as it is.  matrices[b] = matrix(G) rounded once to float32: the value droid_se3_unary gives for INV
+ *     followed by MATRIX up to the rounding of the intermediate record.
+ *  2. Count.  count[k] = droid_depth_filter's count of frame i against its six temporal neighbours inside [0,nbuf),
+ *     with the poses as stored and thresh[b]: the same device code, hence the same bits.
+ *  3. Mean.  mean = sum(disps[i]) / (H W), accumulated in fp64; the order of the sum is free.
+ *  4. Keep rule.  Pixel k is kept iff count[k] >= min_count and (double)disps[i][k] > disp_ratio * mean.
+ *  5. Point.  G (X0 / d), X0 = ((u - cx) / fx, (v - cy) / fy, 1), d = disps[i][k], evaluated in fp64 from the float32
+ *     inputs and rounded once: droid_iproj with the inverted pose, without the float32 rounding of that pose.  Per
+ *     component |out - exact| <= 2^-23 |exact| + 2^-40 S, S = 8 ((|X0x| + |X0y| + 1) / |d| + |t|_1).
+ *  6. Colour (images given).  float(images[i, c, 8v+3, 8u+3]) / 255.0f for c = 2, 1, 0, one IEEE float32 division.
+ * Outputs.  Points come in the order of index, row-major within a frame: exactly the concatenation over b of
+ * points[b].reshape(-1,3)[mask[b]].  A frame selected twice is emitted twice.
+ *   points [P,3] float32 ;  colors [P,3] float32 ;  src [P] int32, the pixel index v W + u of each point ;
+ *   offsets [n+1] int32: offsets[0] = 0, selection b owns rows offsets[b] : offsets[b+1], P = offsets[n] ;
+ *   matrices [n,4,4] float32, row-major.
+ * points, colors and src are capacity buffers of n H W rows; rows at and beyond offsets[n] are NOT written.
+ * Three launches on the stream (decisions per 256-pixel tile, one-workgroup scan of the tile counts, emission); beyond
+ * 65536 tiles the first and the third go out in slabs of that many.  No atomics, no workgroup waits for another: the
+ * same bits on every run.  Every tile's frame mean re-reads the frame (H W floats, from L2).
+ * Workspace: droid_point_cloud_workspace_bytes(n, H, W) bytes (host arithmetic: 36 bytes per tile; 0 for sizes refused
+ * here), 8-byte aligned.  Every word the call reads it has written itself: nothing depends on what the workspace held.
+ * Concurrent calls need separate workspaces.
+ * Refused with DROID_E_ARG and a message naming point_cloud and the argument, before any HIP call, sizes before
+ * pointers: n < 0 ; H or W < 1 ; n H W >= 2^31 ; nbuf < 1 ; then a null poses / disps / intrinsics / index / thresh /
+ * points / src / offsets / matrices ; images without colors or colors without images ; a null, too small or misaligned
+ * workspace ; an output (the workspace included) that shares a byte with an input or with another output.  Any
+ * H, W >= 1 is accepted: a frame with one row or one column keeps nothing (no projection has its four corners inside).
+ * n == 0 launches nothing, touches no pointer and returns 0. */
+size_t droid_point_cloud_workspace_bytes(int n, int H, int W);
+int droid_point_cloud(const float *poses, const float *disps, const float *intrinsics, const int64_t *index,
+                      const float *thresh, const uint8_t *images, int n, int nbuf, int H, int W, int min_count,
+                      double disp_ratio, float *points, float *colors, int *src, int *offsets, float *matrices,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
