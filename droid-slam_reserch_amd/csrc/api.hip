@@ -11,68 +11,7 @@
 #include "../../include/droid_backends_hip.h"
 #include "ba_internal.hpp"
 #include "graph.hpp"
-
-namespace droid {
-// corr.hip
-int launch_corr_index_forward(const void* volume, const float* coords, void* corr, int B, int H1,
-                              int W1, int H2, int W2, int r, int dtype, hipStream_t s);
-int launch_corr_pyramid_forward(const void* const* volumes, const float* coords, void* corr, int B, int H1, int W1,
-                                int r, int levels, int dtype, hipStream_t s);
-int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
-                                      void* corr, int B, int H1, int W1, int r, int levels, int dtype, hipStream_t s);
-int launch_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
-                               int H1, int W1, int H2, int W2, int r, int dtype, hipStream_t s);
-int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t* ii, const int64_t* jj,
-                                   const float* coords, float* corr, int E, int frames, int H, int W, int C,
-                                   int r, int nlevels, int dtype, hipStream_t s);
-int launch_altcorr_forward(const void* f1, const void* f2, const float* coords, void* corr, int B,
-                           int N, int H1, int W1, int H2, int W2, int C, int r, int dtype,
-                           hipStream_t s);
-int launch_altcorr_backward(const float* f1, const float* f2, const float* coords,
-                            const float* corr_grad, float* f1g, float* f2g, int B, int N, int H1,
-                            int W1, int H2, int W2, int C, int r, hipStream_t s);
-// corr_volume.hip
-int launch_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_t* jj, void* const* levels_out, int E,
-                               int nbuf, int ncam, int C, int H, int W, int levels, long long slot0, const int64_t* slots,
-                               long long cap, int dtype, hipStream_t s);
-// geom.hip
-void launch_frame_distance(const float* poses, const float* disps, const float* intr,
-                           const int64_t* ii, const int64_t* jj, int E, int nbuf, int H, int W,
-                           float beta, float* dist, hipStream_t s);
-void launch_frame_distance_matrix(const float* poses, const float* disps, const float* intr, int n, int H, int W,
-                                  float beta, float* dist, hipStream_t s);
-void launch_projmap(const float* poses, const float* disps, const float* intr, const int64_t* ii,
-                    const int64_t* jj, int E, int nbuf, int H, int W, float* coords, float* valid,
-                    hipStream_t s);
-void launch_iproj(const float* poses, const float* disps, const float* intr, int nm, int H, int W,
-                  float* points, hipStream_t s);
-void launch_depth_filter(const float* poses, const float* disps, const float* intr,
-                         const int64_t* ix, const float* thresh, int num, int nbuf, int H, int W,
-                         float* counter, hipStream_t s);
-// upsample.hip
-void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
-                         bool half_mask, hipStream_t s);
-// graph_agg.hip
-size_t graph_mean_workspace_bytes(int E, int range);
-void launch_graph_mean(const void* src, const int64_t* index, void* out, int E, int64_t plane, int M, int range,
-                       int compact, bool half, int* groups_out, void* workspace, hipStream_t s);
-// se3_ops.hip
-void launch_se3_unary(const float* in, float* out, int64_t n, int op, hipStream_t s);
-void launch_se3_mul(const float* a, int stride_a, const float* b, int stride_b, float* out, int64_t n, hipStream_t s);
-void launch_pose_interpolate(const float* poses, const float* tstamp, int N, const float* query, int M, float* out,
-                             int64_t* k0_out, int64_t* k1_out, hipStream_t s);
-// point_cloud.hip
-size_t point_cloud_workspace_bytes(int n, int H, int W);
-void launch_point_cloud(const float* poses, const float* disps, const float* intr, const int64_t* index,
-                        const float* thresh, const uint8_t* images, int n, int nbuf, int H, int W, int min_count,
-                        double disp_ratio, float* points, float* colors, int* src, int* offsets, float* matrices,
-                        void* workspace, hipStream_t s);
-// chol.hip
-void launch_chol_pack(const double* A, const double* b, double* S, int n, int ld, hipStream_t s);
-void launch_reproject_motion(const float* poses, const float* disps, const float* intr, int intr_stride,
-                             const int64_t* ii, const int64_t* jj, const float* target, int E, int nbuf, int H,
-                             int W, float* coords, float* valid, float* motn, hipStream_t s);
-}  // namespace droid
+#include "launchers.hpp"
 
 using namespace droid;
 
@@ -111,12 +50,33 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-static int check_hip(const char* where) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
-    return DROID_E_HIP;
-  }
+static int fail_hip(const char* where, hipError_t e) {
+  return e == hipSuccess ? DROID_OK : fail(DROID_E_HIP, "%s: %s", where, hipGetErrorString(e));
+}
+
+static int check_hip(const char* where) { return fail_hip(where, hipGetLastError()); }
+
+// [p, p + p_bytes) and [q, q + q_bytes) share a byte.  An end beyond the address space saturates.
+static bool bytes_overlap(const void* p, uint64_t p_bytes, const void* q, uint64_t q_bytes) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  const uintptr_t a1 = a + (p_bytes > UINTPTR_MAX - a ? UINTPTR_MAX - a : p_bytes);
+  const uintptr_t b1 = b + (q_bytes > UINTPTR_MAX - b ? UINTPTR_MAX - b : q_bytes);
+  return p_bytes > 0 && q_bytes > 0 && a < b1 && b < a1;
+}
+// bytes of `elems` floats, saturating: a record count near 2^58 times 64 bytes wraps
+static uint64_t f32_bytes(uint64_t elems) { return elems > UINT64_MAX / 4 ? UINT64_MAX : elems * 4; }
+
+static bool null_level(const void* const* levels, int n) {
+  for (int l = 0; l < n; l++)
+    if (!levels[l]) return true;
+  return false;
+}
+
+// sizes, radius and dtype of the corr_index_* / altcorr_* entry points (N = C = 1 where an operator has none)
+static int corr_check(const char* name, int B, int N, int H1, int W1, int H2, int W2, int C, int radius, int dtype) {
+  if (B < 0 || N <= 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0 || C <= 0 || radius < 0 || radius > 7)
+    return fail(DROID_E_ARG, "%s: bad %s", name, "shape/radius");
+  if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "%s: bad %s", name, "dtype");
   return DROID_OK;
 }
 
@@ -128,9 +88,7 @@ const char* droid_last_error(void) { return g_err; }
 // ---------------------------------------------------------------------------- correlation
 int droid_corr_index_forward(const void* volume, const float* coords, void* corr, int B, int H1,
                              int W1, int H2, int W2, int radius, int dtype, void* stream) {
-  if (B < 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0 || radius < 0 || radius > 7)
-    return fail(DROID_E_ARG, "corr_index_forward: bad %s", "shape/radius");
-  if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_index_forward: bad %s", "dtype");
+  if (int rc = corr_check("corr_index_forward", B, 1, H1, W1, H2, W2, 1, radius, dtype)) return rc;
   if (B == 0) return DROID_OK;
   if (!volume || !coords || !corr) return fail(DROID_E_ARG, "corr_index_forward: null %s", "pointer");
   int rc = launch_corr_index_forward(volume, coords, corr, B, H1, W1, H2, W2, radius, dtype,
@@ -145,8 +103,7 @@ int droid_corr_pyramid_forward(const void* const* volumes, const float* coords, 
   if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_pyramid_forward: bad %s", "dtype");
   if (B == 0) return DROID_OK;
   if (!volumes || !coords || !corr) return fail(DROID_E_ARG, "corr_pyramid_forward: null %s", "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!volumes[l]) return fail(DROID_E_ARG, "corr_pyramid_forward: null %s", "pyramid level");
+  if (null_level(volumes, levels)) return fail(DROID_E_ARG, "corr_pyramid_forward: null %s", "pyramid level");
   int rc = launch_corr_pyramid_forward(volumes, coords, corr, B, H1, W1, radius, levels, dtype, (hipStream_t)stream);
   if (rc) return fail(rc, "corr_pyramid_forward: %s", "unsupported configuration (radius 3 or 4, levels that divide the map)");
   return check_hip("corr_pyramid_forward");
@@ -167,8 +124,7 @@ static int corr_volume_pyramid_any(const char* name, bool by_slots, const void* 
   if (E == 0) return DROID_OK;
   if (by_slots && !slots) return fail(DROID_E_ARG, "%s: null %s", name, "slots");
   if (!fmaps || !ii || !jj || !levels_out) return fail(DROID_E_ARG, "%s: null %s", name, "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!levels_out[l]) return fail(DROID_E_ARG, "%s: null %s", name, "pyramid level");
+  if (null_level(levels_out, levels)) return fail(DROID_E_ARG, "%s: null %s", name, "pyramid level");
   int rc = launch_corr_volume_pyramid(fmaps, ii, jj, levels_out, E, nbuf, ncam, C, H, W, levels, (long long)slot0, slots,
                                       (long long)cap, dtype, (hipStream_t)stream);
   if (rc) return fail(rc, "%s: %s", name, "unsupported configuration");
@@ -193,8 +149,7 @@ int droid_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* 
   if (B == 0) return DROID_OK;
   if (!slots) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "slots");
   if (!volumes || !coords || !corr) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!volumes[l]) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "pyramid level");
+  if (null_level(volumes, levels)) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: null %s", "pyramid level");
   int rc = launch_corr_pyramid_forward_slots(volumes, slots, (long long)cap, coords, corr, B, H1, W1, radius, levels, dtype,
                                              (hipStream_t)stream);
   if (rc) return fail(rc, "corr_pyramid_forward_slots: %s", "unsupported configuration");
@@ -210,9 +165,7 @@ int droid_corr_volume_pyramid_slots(const void* fmaps, const int64_t* ii, const 
 
 int droid_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
                               int H1, int W1, int H2, int W2, int radius, int dtype, void* stream) {
-  if (B < 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0 || radius < 0 || radius > 7)
-    return fail(DROID_E_ARG, "corr_index_backward: bad %s", "shape/radius");
-  if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_index_backward: bad %s", "dtype");
+  if (int rc = corr_check("corr_index_backward", B, 1, H1, W1, H2, W2, 1, radius, dtype)) return rc;
   if (B == 0) return DROID_OK;
   if (!coords || !corr_grad || !volume_grad) return fail(DROID_E_ARG, "corr_index_backward: null %s", "pointer");
   int rc = launch_corr_index_backward(coords, corr_grad, volume_grad, B, H1, W1, H2, W2, radius,
@@ -224,9 +177,7 @@ int droid_corr_index_backward(const float* coords, const void* corr_grad, void* 
 int droid_altcorr_forward(const void* fmap1, const void* fmap2, const float* coords, void* corr,
                           int B, int N, int H1, int W1, int H2, int W2, int C, int radius,
                           int dtype, void* stream) {
-  if (B < 0 || N <= 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0 || C <= 0 || radius < 0 || radius > 7)
-    return fail(DROID_E_ARG, "altcorr_forward: bad %s", "shape/radius");
-  if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "altcorr_forward: bad %s", "dtype");
+  if (int rc = corr_check("altcorr_forward", B, N, H1, W1, H2, W2, C, radius, dtype)) return rc;
   if (B == 0) return DROID_OK;
   if (!fmap1 || !fmap2 || !coords || !corr) return fail(DROID_E_ARG, "altcorr_forward: null %s", "pointer");
   int rc = launch_altcorr_forward(fmap1, fmap2, coords, corr, B, N, H1, W1, H2, W2, C, radius,
@@ -242,8 +193,7 @@ static int altcorr_pyramid_any(const void* const* pyramid, const int64_t* ii, co
     return fail(DROID_E_ARG, "altcorr_pyramid_forward: bad %s", "shape");
   if (E == 0) return DROID_OK;
   if (!pyramid || !ii || !jj || !coords || !corr) return fail(DROID_E_ARG, "altcorr_pyramid_forward: null %s", "pointer");
-  for (int l = 0; l < levels; l++)
-    if (!pyramid[l]) return fail(DROID_E_ARG, "altcorr_pyramid_forward: null %s", "pyramid level");
+  if (null_level(pyramid, levels)) return fail(DROID_E_ARG, "altcorr_pyramid_forward: null %s", "pyramid level");
   int rc = launch_altcorr_pyramid_forward(pyramid, ii, jj, coords, corr, E, frames, H, W, C, radius, levels, dtype,
                                           (hipStream_t)stream);
   if (rc) return fail(rc, "altcorr_pyramid_forward: %s", "unsupported configuration (C % 16 (fp32) / 32 (fp16) == 0, C <= 128, r in {3,4})");
@@ -266,8 +216,7 @@ int droid_altcorr_pyramid_forward_f16(const void* const* pyramid, const int64_t*
 int droid_altcorr_backward(const float* fmap1, const float* fmap2, const float* coords,
                            const float* corr_grad, float* fmap1_grad, float* fmap2_grad, int B,
                            int N, int H1, int W1, int H2, int W2, int C, int radius, void* stream) {
-  if (B < 0 || N <= 0 || H1 <= 0 || W1 <= 0 || H2 <= 0 || W2 <= 0 || C <= 0 || radius < 0 || radius > 7)
-    return fail(DROID_E_ARG, "altcorr_backward: bad %s", "shape/radius");
+  if (int rc = corr_check("altcorr_backward", B, N, H1, W1, H2, W2, C, radius, DROID_F32)) return rc;   // fp32 only
   if (B == 0) return DROID_OK;
   if (!fmap1 || !fmap2 || !coords || !corr_grad || !fmap1_grad || !fmap2_grad)
     return fail(DROID_E_ARG, "altcorr_backward: null %s", "pointer");
@@ -534,10 +483,7 @@ int droid_ba_profile_iteration(float* poses, float* disps, const float* intrinsi
   for (int k = 0; k < 6; k++) (void)hipEventElapsedTime(&stage_ms[k < 3 ? k : k + 1], ev[k], ev[k + 1]);
   (void)hipEventElapsedTime(&stage_ms[7], ev[0], ev[6]);
   for (auto& x : ev) (void)hipEventDestroy(x);
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "ba_profile: %s", hipGetErrorString(e));
-    return DROID_E_HIP;
-  }
+  if (e != hipSuccess) return fail_hip("ba_profile", e);
   return check_hip("ba_profile_iteration");
 }
 
@@ -555,10 +501,7 @@ int droid_ba_status(const void* workspace, void* stream, int* status_out, int* d
   int hdr[HDR_WORDS];
   hipError_t e = hipMemcpyAsync(hdr, workspace, sizeof(hdr), hipMemcpyDeviceToHost, (hipStream_t)stream);
   if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "ba_status: %s", hipGetErrorString(e));
-    return DROID_E_HIP;
-  }
+  if (e != hipSuccess) return fail_hip("ba_status", e);
   if (status_out) *status_out = hdr[HDR_STATUS];
   if (depth_slots_out) *depth_slots_out = hdr[HDR_M];
   return DROID_OK;
@@ -767,15 +710,6 @@ int droid_proximity_edges(const float* dist, int ld, int bidirectional, int t, i
 }
 
 // ---- pose algebra (se3_ops.hip) ---------------------------------------------------------------------------------
-// [p, p + elems * 4 bytes) and [q, ...) share a byte.  Saturating: a record count near 2^58 times 64 bytes wraps.
-static bool f32_overlap(const void* p, uint64_t p_elems, const void* q, uint64_t q_elems, unsigned q_elem_bytes = 4) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  const uint64_t room_a = UINTPTR_MAX - a, room_b = UINTPTR_MAX - b;
-  const uintptr_t a1 = a + (p_elems > room_a / 4 ? room_a : p_elems * 4);
-  const uintptr_t b1 = b + (q_elems > room_b / q_elem_bytes ? room_b : q_elems * q_elem_bytes);
-  return p_elems > 0 && q_elems > 0 && a < b1 && b < a1;
-}
-
 int droid_se3_unary(const float* in, float* out, int64_t n, int op, void* stream) {
   if (op < DROID_SE3_INV || op > DROID_SE3_MATRIX) return fail(DROID_E_ARG, "se3_unary: bad %s", "op (0 .. 3)");
   if (n < 0) return fail(DROID_E_ARG, "se3_unary: bad %s", "n (negative)");
@@ -784,7 +718,7 @@ int droid_se3_unary(const float* in, float* out, int64_t n, int op, void* stream
   if (!in || !out) return fail(DROID_E_ARG, "se3_unary: null %s", "pointer (in / out)");
   const int win = op == DROID_SE3_EXP ? 6 : 7;
   const int wout = op == DROID_SE3_LOG ? 6 : op == DROID_SE3_MATRIX ? 16 : 7;
-  if (!(op == DROID_SE3_INV && in == out) && f32_overlap(in, (uint64_t)n * win, out, (uint64_t)n * wout))
+  if (!(op == DROID_SE3_INV && in == out) && bytes_overlap(in, f32_bytes((uint64_t)n * win), out, f32_bytes((uint64_t)n * wout)))
     return fail(DROID_E_ARG, "se3_unary: %s", "out overlaps in (only INV may run in place, with out == in)");
   launch_se3_unary(in, out, n, op, (hipStream_t)stream);
   return check_hip("se3_unary");
@@ -797,9 +731,9 @@ int droid_se3_mul(const float* a, int stride_a, const float* b, int stride_b, fl
   if (n > ((int64_t)1 << 62) / 16) return fail(DROID_E_ARG, "se3_mul: %s", "n * 16 exceeds the kernel's index range (2^62)");
   if (n == 0) return DROID_OK;
   if (!a || !b || !out) return fail(DROID_E_ARG, "se3_mul: null %s", "pointer (a / b / out)");
-  if (!(stride_a == 7 && a == out) && f32_overlap(a, stride_a ? (uint64_t)n * 7 : 7, out, (uint64_t)n * 7))
+  if (!(stride_a == 7 && a == out) && bytes_overlap(a, stride_a ? (uint64_t)n * 28 : 28, out, (uint64_t)n * 28))
     return fail(DROID_E_ARG, "se3_mul: %s", "out overlaps a (allowed: out == a with stride_a = 7)");
-  if (!(stride_b == 7 && b == out) && f32_overlap(b, stride_b ? (uint64_t)n * 7 : 7, out, (uint64_t)n * 7))
+  if (!(stride_b == 7 && b == out) && bytes_overlap(b, stride_b ? (uint64_t)n * 28 : 28, out, (uint64_t)n * 28))
     return fail(DROID_E_ARG, "se3_mul: %s", "out overlaps b (allowed: out == b with stride_b = 7)");
   launch_se3_mul(a, stride_a, b, stride_b, out, n, (hipStream_t)stream);
   return check_hip("se3_mul");
@@ -811,12 +745,12 @@ int droid_pose_interpolate(const float* poses, const float* tstamp, int N, const
   if (M < 0) return fail(DROID_E_ARG, "pose_interpolate: bad %s", "M (negative)");
   if (M == 0) return DROID_OK;
   if (!poses || !tstamp || !query || !out) return fail(DROID_E_ARG, "pose_interpolate: null %s", "pointer (poses / tstamp / query / out)");
-  const struct { const void* p; uint64_t elems; unsigned bytes; const char* name; } outs[3] = {
-      {out, (uint64_t)M * 7, 4, "out"}, {k0_out, (uint64_t)M, 8, "k0_out"}, {k1_out, (uint64_t)M, 8, "k1_out"}};
+  const struct { const void* p; uint64_t bytes; const char* name; } outs[3] = {
+      {out, (uint64_t)M * 28, "out"}, {k0_out, (uint64_t)M * 8, "k0_out"}, {k1_out, (uint64_t)M * 8, "k1_out"}};
   for (const auto& o : outs) {
     if (!o.p) continue;
-    if (f32_overlap(poses, (uint64_t)N * 7, o.p, o.elems, o.bytes) || f32_overlap(tstamp, (uint64_t)N, o.p, o.elems, o.bytes) ||
-        f32_overlap(query, (uint64_t)M, o.p, o.elems, o.bytes))
+    if (bytes_overlap(poses, (uint64_t)N * 28, o.p, o.bytes) || bytes_overlap(tstamp, (uint64_t)N * 4, o.p, o.bytes) ||
+        bytes_overlap(query, (uint64_t)M * 4, o.p, o.bytes))
       return fail(DROID_E_ARG, "pose_interpolate: %s overlaps an input (poses / tstamp / query)", o.name);
   }
   launch_pose_interpolate(poses, tstamp, N, query, M, out, k0_out, k1_out, (hipStream_t)stream);
@@ -863,17 +797,13 @@ int droid_point_cloud(const float* poses, const float* disps, const float* intri
   const Range outs[6] = {{points, cap * 12, "points"}, {colors, colors ? cap * 12 : 0, "colors"}, {src, cap * 4, "src"},
                          {offsets, ((uint64_t)n + 1) * 4, "offsets"}, {matrices, (uint64_t)n * 64, "matrices"},
                          {workspace, point_cloud_workspace_bytes(n, H, W), "workspace"}};
-  auto overlap = [](const Range& a, const Range& b) {   // share a byte; an end beyond the address space saturates
-    const uintptr_t a0 = (uintptr_t)a.p, b0 = (uintptr_t)b.p;
-    const uintptr_t a1 = a0 + (a.bytes > UINTPTR_MAX - a0 ? UINTPTR_MAX - a0 : a.bytes);
-    const uintptr_t b1 = b0 + (b.bytes > UINTPTR_MAX - b0 ? UINTPTR_MAX - b0 : b.bytes);
-    return a.bytes > 0 && b.bytes > 0 && a0 < b1 && b0 < a1;
-  };
   for (int o = 0; o < 6; o++) {
+    const Range& out = outs[o];
     for (const Range& in : ins)
-      if (overlap(outs[o], in)) return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", outs[o].name, in.name);
+      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", out.name, in.name);
     for (int q = 0; q < o; q++)
-      if (overlap(outs[o], outs[q])) return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", outs[o].name, outs[q].name);
+      if (bytes_overlap(out.p, out.bytes, outs[q].p, outs[q].bytes))
+        return fail(DROID_E_ARG, "point_cloud: %s overlaps %s", out.name, outs[q].name);
   }
   launch_point_cloud(poses, disps, intrinsics, index, thresh, images, n, nbuf, H, W, min_count, disp_ratio, points, colors,
                      src, offsets, matrices, workspace, (hipStream_t)stream);

@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "ba_internal.hpp"
+#include "launchers.hpp"
 
 namespace droid {
 

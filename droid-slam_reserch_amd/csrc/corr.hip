@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/droid_backends_hip.h"
+#include "launchers.hpp"
 
 // The rounding points are part of the contract: no fused multiply-add and no mixed-precision
 // folding (hipcc's default -ffp-contract=fast turns round_f16(a*b) into v_fma_mixlo_f16, which

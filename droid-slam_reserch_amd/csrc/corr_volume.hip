@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "../../include/droid_backends_hip.h"
+#include "launchers.hpp"
 
 namespace droid {
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.hpp"
 #include "se3.hpp"
 
 namespace droid {

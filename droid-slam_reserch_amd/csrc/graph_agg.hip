@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/droid_backends_hip.h"
+#include "launchers.hpp"
 
 namespace droid {
 

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/droid_backends_hip.h"
+#include "launchers.hpp"
 #include "se3.hpp"
 
 namespace droid {

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launchers.hpp"
+
 namespace droid {
 
 __device__ __forceinline__ float cvx_logit(const __half* p) { return __half2float(*p); }   // exact widening

@@ -15,6 +15,7 @@ import os as _os
 import torch
 
 from . import _lib
+from ._args import ScratchCache, _ptr, _stream, _ws_key, check_tensors
 from ._lib import DroidBackendError  # noqa: F401
 from .ba_binding import BAProblemDev, BaBinding, read_status
 from . import se3
@@ -43,38 +44,12 @@ _workspaces = {}   # (device index, stream handle) -> BaBinding: grow-only scrat
 _SYNC_CHECK = _os.environ.get("DROID_HIP_CHECK", "0") == "1"
 
 
-def _check_input(x, name):
-    # CHECK_CONTIGUOUS, droid.cpp:84-85
-    if not x.is_contiguous():
-        raise RuntimeError(f"{name} must be contiguous")
-    if not x.is_cuda:
-        raise RuntimeError(f"{name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
+F32, I64, F16_OR_F32 = torch.float32, torch.int64, (torch.float16, torch.float32)
 
 
-def _check_index(x, name):
-    """The kernels read edge / frame indices as int64 (torch.long, like the reference's accessors)."""
-    _check_input(x, name)
-    if x.dtype != torch.int64:
-        raise RuntimeError(f"{name} must be int64 (torch.long), got {x.dtype}")
-
-
-def _check_f32(x, name):
-    _check_input(x, name)
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32, got {x.dtype}")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _ws_key(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    return (idx, torch.cuda.current_stream(idx).cuda_stream)
+def _state(poses, disps, intrinsics):
+    """The three float32 tensors most operators start with, as `check_tensors` takes them."""
+    return [(poses, "poses", F32), (disps, "disps", F32), (intrinsics, "intrinsics", F32)]
 
 
 def _workspace_obj(device):
@@ -117,15 +92,8 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
     made contiguous here because the kernels index it directly.
     """
     _lib.load()
-    for x, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
-                 (intrinsics, "intrinsics"), (disps_sens, "disps_sens"), (ii, "ii"), (jj, "jj")):
-        _check_input(x, n)
-    if ii.dtype != torch.int64 or jj.dtype != torch.int64:
-        raise RuntimeError("ii and jj must be int64")
-    for x, n in ((targets, "targets"), (weights, "weights"), (poses, "poses"), (disps, "disps"),
-                 (intrinsics, "intrinsics"), (disps_sens, "disps_sens")):
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be float32")
+    check_tensors("ba", [(targets, "targets", F32), (weights, "weights", F32), (poses, "poses", F32), (disps, "disps", F32),
+                         (intrinsics, "intrinsics", F32), (disps_sens, "disps_sens", F32), (ii, "ii", I64), (jj, "jj", I64)])
     motion_only = bool(motion_only)
     H, W = disps.shape[1:]
     dev = poses.device
@@ -152,10 +120,7 @@ def ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, 
 def frame_distance(poses, disps, intrinsics, ii, jj, beta):
     """droid.cpp:120-136 -> frame_distance_cuda droid_kernels.cu:1438-1460."""
     lib = _lib.load()
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-        _check_f32(x, n)
-    _check_index(ii, "ii")
-    _check_index(jj, "jj")
+    check_tensors("frame_distance", _state(poses, disps, intrinsics) + [(ii, "ii", I64), (jj, "jj", I64)])
     nbuf, H, W = disps.shape
     nbuf = min(int(nbuf), int(poses.shape[0]))
     E = int(ii.shape[0])
@@ -172,8 +137,7 @@ def frame_distance_matrix(poses, disps, intrinsics, n, beta, bidirectional=True)
     `bidirectional` (the reference's default), else frame_distance(i -> j).  No meshgrid index tensors, one kernel
     instead of two, each depth map fetched once per 32 targets.  An addition."""
     lib = _lib.load()
-    for x, nm in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-        _check_f32(x, nm)
+    check_tensors("frame_distance_matrix", _state(poses, disps, intrinsics))
     nbuf, H, W = disps.shape
     nbuf = min(int(nbuf), int(poses.shape[0]))
     n = int(n)
@@ -184,7 +148,7 @@ def frame_distance_matrix(poses, disps, intrinsics, n, beta, bidirectional=True)
     return .5 * (d + d.t()) if bidirectional else d
 
 
-_prox_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of proximity_edges
+_prox_ws = ScratchCache()   # _ws_key(device) -> grow-only uint8 scratch of proximity_edges
 
 
 def _forced_before(i, m):
@@ -215,34 +179,28 @@ def proximity_edges(poses, disps, intrinsics, t, t0, t1, rad, nms, beta, thresh,
     count is read back to size the result."""
     lib = _lib.load()
     t, t0, t1, rad, nms, max_factors = int(t), int(t0), int(t1), int(rad), int(nms), int(max_factors)
-    _check_index(sup_ii, "sup_ii")
-    _check_index(sup_jj, "sup_jj")
     if (known_ii is None) != (known_jj is None):
         raise RuntimeError("proximity_edges: known_ii and known_jj go together")
+    lists = [(sup_ii, "sup_ii", I64), (sup_jj, "sup_jj", I64)]
     if known_ii is not None:
-        _check_index(known_ii, "known_ii")
-        _check_index(known_jj, "known_jj")
+        lists += [(known_ii, "known_ii", I64), (known_jj, "known_jj", I64)]
     if dist is None:
-        for x, nm in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-            _check_f32(x, nm)
+        check_tensors("proximity_edges", lists + _state(poses, disps, intrinsics))
         dist = frame_distance_matrix(poses, disps, intrinsics, t, beta, bidirectional=False)
     else:
-        if not dist.is_cuda:
-            raise RuntimeError("dist must be a HIP (cuda) tensor: droid_backends has no CPU path")
+        check_tensors("proximity_edges", lists)
         if dist.dtype != torch.float32 or dist.dim() != 2 or (dist.numel() and dist.stride(1) != 1):
             raise RuntimeError("proximity_edges: dist must be a float32 matrix with unit column stride")
         if dist.shape[0] < t or dist.shape[1] < t:
             raise RuntimeError("proximity_edges: dist is smaller than [t, t]")
+        check_tensors("proximity_edges", [(dist, "dist", None)], types=False, contiguous=False)   # rows may be padded
     dev = dist.device
     n_sup, n_known = int(sup_ii.shape[0]), 0 if known_ii is None else int(known_ii.shape[0])
     if int(sup_jj.shape[0]) != n_sup or (n_known and int(known_jj.shape[0]) != n_known):
         raise RuntimeError("proximity_edges: ii and jj of an edge list must have one length")
     cap = proximity_edge_bound(t, t0, t1, rad, max_factors, bool(stereo))
     nbytes = lib.droid_proximity_workspace_bytes(t, t0, t1, n_known, cap)
-    key = _ws_key(dev)
-    ws = _prox_ws.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _prox_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+    ws = _prox_ws.get_bytes(_ws_key(dev), nbytes, dev)
     out = torch.empty((cap, 2), dtype=torch.int64, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     ld = int(dist.stride(0)) if dist.shape[0] > 1 else max(int(dist.shape[1]), t)
@@ -258,10 +216,7 @@ def proximity_edges(poses, disps, intrinsics, t, t0, t1, rad, nms, beta, thresh,
 def projmap(poses, disps, intrinsics, ii, jj):
     """droid.cpp:139-154 -> projmap_cuda droid_kernels.cu:1463-1488."""
     lib = _lib.load()
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-        _check_f32(x, n)
-    _check_index(ii, "ii")
-    _check_index(jj, "jj")
+    check_tensors("projmap", _state(poses, disps, intrinsics) + [(ii, "ii", I64), (jj, "jj", I64)])
     nbuf, H, W = disps.shape
     nbuf = min(int(nbuf), int(poses.shape[0]))
     E = int(ii.shape[0])
@@ -280,13 +235,8 @@ def reproject(poses, disps, intrinsics, ii, jj, target=None):
     (or [E,H,W,2]) the motion features of factor_graph.py:203-205 are produced in the same pass and returned as
     a third tensor [1,E,4,H,W]."""
     lib = _lib.load()
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (ii, "ii"), (jj, "jj")):
-        _check_input(x, n)
-    if ii.dtype != torch.int64 or jj.dtype != torch.int64:
-        raise RuntimeError("ii and jj must be int64")
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")) + (((target, "target"),) if target is not None else ()):
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"{n} must be float32")
+    check_tensors("reproject", _state(poses, disps, intrinsics) + [(ii, "ii", I64), (jj, "jj", I64)]
+                  + ([(target, "target", F32)] if target is not None else []))
     if poses.dim() == 3:  # accept the batched [1,nbuf,...] tensors the caller holds
         poses, disps = poses[0], disps[0]
         if intrinsics.dim() == 3:
@@ -304,7 +254,6 @@ def reproject(poses, disps, intrinsics, ii, jj, target=None):
     motn = None
     tptr = None
     if target is not None:
-        _check_input(target, "target")
         target = target.reshape(E, H, W, 2).contiguous()
         motn = torch.empty((1, E, 4, H, W), dtype=torch.float32, device=poses.device)
         tptr = target.data_ptr()
@@ -325,9 +274,7 @@ def motion_features(poses, disps, intrinsics, ii, jj, target):
 def depth_filter(poses, disps, intrinsics, ix, thresh):
     """droid.cpp:220-234 -> depth_filter_cuda droid_kernels.cu:1491-1515."""
     lib = _lib.load()
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (thresh, "thresh")):
-        _check_f32(x, n)
-    _check_index(ix, "ix")
+    check_tensors("depth_filter", _state(poses, disps, intrinsics) + [(thresh, "thresh", F32), (ix, "ix", I64)])
     nbuf, H, W = disps.shape
     nbuf = min(int(nbuf), int(poses.shape[0]))
     num = int(ix.shape[0])
@@ -341,8 +288,7 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
 def iproj(poses, disps, intrinsics):
     """droid.cpp:157-166 -> iproj_cuda droid_kernels.cu:1518-1541."""
     lib = _lib.load()
-    for x, n in ((poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics")):
-        _check_f32(x, n)
+    check_tensors("iproj", _state(poses, disps, intrinsics))
     nm, H, W = disps.shape
     points = torch.empty((nm, H, W, 3), dtype=torch.float32, device=disps.device)
     _lib.check(lib.droid_iproj(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), nm, H, W,
@@ -350,7 +296,7 @@ def iproj(poses, disps, intrinsics):
     return points
 
 
-_pc_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of point_cloud
+_pc_ws = ScratchCache()   # _ws_key(device) -> grow-only uint8 scratch of point_cloud
 
 
 class PointCloud:
@@ -383,18 +329,12 @@ def point_cloud(poses, disps, intrinsics, index, thresh, images=None, min_count=
     No autograd.  An addition."""
     lib = _lib.load()
     what = "point_cloud"
-    tensors = [(poses, "poses"), (disps, "disps"), (intrinsics, "intrinsics"), (index, "index")]
+    tensors = _state(poses, disps, intrinsics) + [(index, "index", I64)]
     if isinstance(thresh, torch.Tensor):
-        tensors.append((thresh, "thresh"))
+        tensors.append((thresh, "thresh", F32))
     if images is not None:
-        tensors.append((images, "images"))
-    for x, name in tensors:
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{what}: {name} must be a tensor, got {type(x).__name__}")
-    for x, name in tensors:
-        want = torch.int64 if name == "index" else torch.uint8 if name == "images" else torch.float32
-        if x.dtype != want:
-            raise RuntimeError(f"{what}: {name} must be {str(want).replace('torch.', '')}, got {x.dtype}")
+        tensors.append((images, "images", torch.uint8))
+    check_tensors(what, tensors, placement=False)
     if poses.dim() != 2 or poses.shape[1] != 7 or disps.dim() != 3 or intrinsics.dim() != 1 or intrinsics.shape[0] != 4:
         raise RuntimeError(f"{what}: poses must be [nbuf, 7], disps [nbuf, h, w], intrinsics [4], got "
                            f"{tuple(poses.shape)}, {tuple(disps.shape)}, {tuple(intrinsics.shape)}")
@@ -407,14 +347,7 @@ def point_cloud(poses, disps, intrinsics, index, thresh, images=None, min_count=
     if images is not None and tuple(images.shape) != (nbuf, 3, 8 * h, 8 * w):
         raise RuntimeError(f"{what}: images must be [{nbuf}, 3, {8 * h}, {8 * w}] for {nbuf} frames of {h} x {w}, got "
                            f"{tuple(images.shape)}")
-    for x, name in tensors:
-        if not x.is_contiguous():
-            raise RuntimeError(f"{what}: {name} must be contiguous")
-    for x, name in tensors:
-        if not x.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
-        if x.device != disps.device:
-            raise RuntimeError(f"{what}: {name} is on {x.device}, disps on {disps.device}")
+    check_tensors(what, tensors, types=False, on=(disps, "disps"))
     if h < 1 or w < 1:
         raise RuntimeError(f"{what}: disps must have h, w >= 1, got {tuple(disps.shape)}")
     if n * h * w >= 2 ** 31:
@@ -436,11 +369,7 @@ def point_cloud(poses, disps, intrinsics, index, thresh, images=None, min_count=
                               [0] * (n + 1) if sync else None)
         offsets = torch.empty((n + 1,), dtype=torch.int32, device=dev)
         stream = _stream()
-        nbytes = lib.droid_point_cloud_workspace_bytes(n, h, w)
-        key = (dev.index, stream)
-        ws = _pc_ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _pc_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+        ws = _pc_ws.get_bytes(_ws_key(dev), lib.droid_point_cloud_workspace_bytes(n, h, w), dev)
         _lib.check(lib.droid_point_cloud(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), index.data_ptr(),
                                          thresh.data_ptr(), _ptr(images), n, nbuf, h, w, int(min_count), float(disp_ratio),
                                          points.data_ptr(), _ptr(colors), src.data_ptr(), offsets.data_ptr(),
@@ -456,28 +385,17 @@ def _upsample_args(what, mask, n, h, w, f32, ix=None):
     """Checks of a convex upsampling, shapes and dtypes before devices so that a caller's mistake is named as what it
     is: f32 = ((tensor, name), ...) must be contiguous float32; the mask is returned as [n, 576, h, w], half or fp32
     (droid_cvx_upsample); every tensor must be on one HIP device."""
-    for x, name in f32:
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"{what}: {name} must be float32, got {x.dtype}")
-    if ix is not None and ix.dtype != torch.int64:
-        raise RuntimeError(f"{what}: ix must be int64 (torch.long), got {ix.dtype}")
-    if mask.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"{what}: mask must be float16 or float32, got {mask.dtype}")
-    for x, name in f32 + ((mask, "mask"),) + (((ix, "ix"),) if ix is not None else ()):
-        if not x.is_contiguous():
-            raise RuntimeError(f"{what}: {name} must be contiguous")
     if mask.dim() == 5 and mask.shape[0] == 1:
         mask = mask[0]
+    tensors = ([(x, name, F32) for x, name in f32] + ([(ix, "ix", I64)] if ix is not None else [])
+               + [(mask, "mask", F16_OR_F32)])
+    check_tensors(what, tensors, placement=False)
     if mask.dim() != 4 or mask.shape[-3] != 576:
         raise RuntimeError(f"{what}: mask must be [1, n, 576, h, w] or [n, 576, h, w] (9 taps x 8 x 8 sub-pixels), got "
                            f"{tuple(mask.shape)}")
     if tuple(mask.shape) != (n, 576, h, w):
         raise RuntimeError(f"{what}: mask must be [{n}, 576, {h}, {w}] for {n} frames of {h} x {w}, got {tuple(mask.shape)}")
-    for x, name in f32 + ((mask, "mask"),) + (((ix, "ix"),) if ix is not None else ()):
-        if not x.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
-        if x.device != mask.device:
-            raise RuntimeError(f"{what}: {name} is on {x.device}, the mask on {mask.device}")
+    check_tensors(what, tensors, types=False, on=(mask, "the mask"))
     return mask
 
 
@@ -524,32 +442,23 @@ def cvx_upsample(data, mask):
     return out
 
 
-_gm_ws = {}   # (device index, stream handle) -> grow-only uint8 scratch of graph_mean / scatter_mean
+_gm_ws = ScratchCache()   # _ws_key(device) -> grow-only uint8 scratch of graph_mean / scatter_mean
 
 
 def _graph_mean_args(what, src, index, batched):
     """The checks both entry points share, a caller's mistake named before the device is looked at.  Returns src as
     [E, ...] rows (src[0] when `batched`: [1, E, ...])."""
-    if src.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"{what}: src must be float16 or float32, got {src.dtype}")
-    if index.dtype != torch.int64:
-        raise RuntimeError(f"{what}: index must be int64 (torch.long), got {index.dtype}")
+    tensors = [(src, "src", F16_OR_F32), (index, "index", I64)]
+    check_tensors(what, tensors, placement=False)
     if torch.is_grad_enabled() and src.requires_grad:
         raise RuntimeError(f"{what}: no autograd -- training keeps torch_scatter (inference only)")
-    for x, name in ((src, "src"), (index, "index")):
-        if not x.is_contiguous():
-            raise RuntimeError(f"{what}: {name} must be contiguous")
     if batched and src.shape[0] != 1:
         raise RuntimeError(f"{what}: batch must be 1, got {int(src.shape[0])}")
     rows = src[0] if batched else src
     if index.dim() != 1 or int(index.shape[0]) != int(rows.shape[0]):
         raise RuntimeError(f"{what}: index must be [E] = [{int(rows.shape[0])}], one group per row of src, got "
                            f"{tuple(index.shape)}")
-    for x, name in ((src, "src"), (index, "index")):
-        if not x.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
-    if index.device != src.device:
-        raise RuntimeError(f"{what}: index is on {index.device}, src on {src.device}")
+    check_tensors(what, tensors, types=False, on=(src, "src"))
     return rows
 
 
@@ -566,10 +475,7 @@ def _graph_mean_run(what, rows, batched, index, M, rng, compact):
     ws, stream = None, _stream()
     if E > 0:
         nbytes = lib.droid_graph_mean_workspace_bytes(E, rng)   # 0 for sizes the call below refuses by name
-        key = (dev.index, stream)
-        ws = _gm_ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _gm_ws[key] = torch.empty(max(int(nbytes * 1.25), 4096), dtype=torch.uint8, device=dev)
+        ws = _gm_ws.get_bytes(_ws_key(dev), nbytes, dev)
     _lib.check(lib.droid_graph_mean(rows.data_ptr() if E else None, index.data_ptr() if E else None, out.data_ptr(),
                                     E, plane, M, rng, compact, _DT[rows.dtype], None, _ptr(ws),
                                     ws.numel() if ws is not None else 0, stream), what)
@@ -623,10 +529,7 @@ def _corr_dtype(t, name):
 def corr_index_forward(volume, coords, radius):
     """droid.cpp:170-178 -> corr_index_cuda_forward correlation_kernels.cu:126-155."""
     lib = _lib.load()
-    _check_input(volume, "volume")
-    _check_input(coords, "coords")
-    if coords.dtype != torch.float32:
-        raise RuntimeError("coords must be float32")
+    check_tensors("corr_index_forward", [(volume, "volume", None), (coords, "coords", F32)])
     B, H1, W1, H2, W2 = volume.shape
     r = int(radius)
     corr = torch.empty((B, 2 * r + 1, 2 * r + 1, H1, W1), dtype=volume.dtype, device=volume.device)
@@ -646,18 +549,16 @@ def corr_pyramid_forward(pyramid, coords, radius, slots=None):
     without the gathered copy; a slot outside [0, cap) gives zeros for that entry (droid_corr_pyramid_forward_slots)."""
     lib = _lib.load()
     levels = list(pyramid)
-    for i, p in enumerate(levels):
-        _check_input(p, f"pyramid[{i}]")
-        if p.dtype != levels[0].dtype:
-            raise RuntimeError("corr_pyramid_forward: pyramid levels must share one dtype")
-    _check_f32(coords, "coords")
+    check_tensors("corr_pyramid_forward", [(p, f"pyramid[{i}]", None) for i, p in enumerate(levels)]
+                  + [(coords, "coords", F32)] + ([(slots, "slots", I64)] if slots is not None else []))
+    if any(p.dtype != levels[0].dtype for p in levels):
+        raise RuntimeError("corr_pyramid_forward: pyramid levels must share one dtype")
     cap, H1, W1 = int(levels[0].shape[0]), int(levels[0].shape[1]), int(levels[0].shape[2])
     for l, p in enumerate(levels):
         if tuple(p.shape) != (cap, H1, W1, H1 >> l, W1 >> l):
             raise RuntimeError(f"corr_pyramid_forward: pyramid[{l}] must be [{cap},{H1},{W1},{H1 >> l},{W1 >> l}]")
     B = cap
     if slots is not None:
-        _check_index(slots, "slots")
         if slots.dim() != 1:
             raise RuntimeError("corr_pyramid_forward: slots must be [B]")
         B = int(slots.shape[0])
@@ -690,11 +591,8 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0, slots=None)
     edge whose slot is outside [0, cap) is skipped, and `out` itself is returned (droid_corr_volume_pyramid_slots).
     The contract is in include/droid_backends_hip.h (droid_corr_volume_pyramid).  An addition."""
     lib = _lib.load()
-    _check_input(fmaps, "fmaps")
-    _check_index(ii, "ii")
-    _check_index(jj, "jj")
-    if fmaps.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"corr_volume_pyramid: fmaps must be float16 or float32, got {fmaps.dtype}")
+    check_tensors("corr_volume_pyramid", [(fmaps, "fmaps", F16_OR_F32), (ii, "ii", I64), (jj, "jj", I64)]
+                  + ([(slots, "slots", I64)] if slots is not None else []))
     if fmaps.dim() == 4:
         fmaps = fmaps[:, None]
     if fmaps.dim() != 5:
@@ -714,8 +612,8 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0, slots=None)
         out = list(out)
         if len(out) != levels:
             raise RuntimeError(f"corr_volume_pyramid: out must hold {levels} levels")
+        check_tensors("corr_volume_pyramid", [(o, f"out[{l}]", None) for l, o in enumerate(out)])
         for l, o in enumerate(out):
-            _check_input(o, f"out[{l}]")
             if o.dtype != fmaps.dtype or o.dim() != 5 or tuple(o.shape[1:]) != shapes[l] or o.shape[0] != out[0].shape[0]:
                 raise RuntimeError(f"corr_volume_pyramid: out[{l}] must be [cap,{h},{w},{h >> l},{w >> l}] of {fmaps.dtype}")
     cap = int(out[0].shape[0]) if levels > 0 else 0
@@ -724,7 +622,6 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0, slots=None)
             raise RuntimeError("corr_volume_pyramid: slots needs out")
         if offset != 0:
             raise RuntimeError("corr_volume_pyramid: slots and offset exclude each other")
-        _check_index(slots, "slots")
         if tuple(slots.shape) != (E,):
             raise RuntimeError("corr_volume_pyramid: slots must be [E]")
         ptrs = (ctypes.c_void_p * max(levels, 1))(*[o.data_ptr() for o in out])
@@ -743,9 +640,7 @@ def corr_volume_pyramid(fmaps, ii, jj, levels=4, out=None, offset=0, slots=None)
 def corr_index_backward(volume, coords, corr_grad, radius):
     """droid.cpp:180-191 -> corr_index_cuda_backward correlation_kernels.cu:157-185."""
     lib = _lib.load()
-    _check_input(volume, "volume")
-    _check_f32(coords, "coords")
-    _check_input(corr_grad, "corr_grad")
+    check_tensors("corr_index_backward", [(volume, "volume", None), (coords, "coords", F32), (corr_grad, "corr_grad", None)])
     B, H1, W1, H2, W2 = volume.shape
     if corr_grad.dtype != volume.dtype:
         corr_grad = corr_grad.to(volume.dtype)
@@ -759,9 +654,7 @@ def corr_index_backward(volume, coords, corr_grad, radius):
 def altcorr_forward(fmap1, fmap2, coords, radius):
     """droid.cpp:193-203 -> altcorr_cuda_forward altcorr_kernel.cu:290-319."""
     lib = _lib.load()
-    _check_input(fmap1, "fmap1")
-    _check_input(fmap2, "fmap2")
-    _check_input(coords, "coords")
+    check_tensors("altcorr_forward", [(fmap1, "fmap1", None), (fmap2, "fmap2", None), (coords, "coords", None)])
     if fmap2.dtype != fmap1.dtype or coords.dtype != torch.float32:
         raise RuntimeError("altcorr_forward: fmap dtypes must match and coords must be float32")
     B, N, H, W, _ = coords.shape
@@ -790,13 +683,10 @@ def altcorr_pyramid_forward(pyramid, coords, ii, jj, radius):
     levels = [p[0] if p.dim() == 5 else p for p in pyramid]
     if coords.dim() == 5:
         coords = coords[0]
-    for i, p in enumerate(levels):
-        _check_input(p, f"pyramid[{i}]")
-        if p.dtype != levels[0].dtype or p.dtype not in (torch.float32, torch.float16):
-            raise RuntimeError("altcorr_pyramid_forward: pyramid levels must all be float32 or all float16")
-    _check_input(coords, "coords")
-    _check_input(ii, "ii")
-    _check_input(jj, "jj")
+    check_tensors("altcorr_pyramid_forward", [(p, f"pyramid[{i}]", None) for i, p in enumerate(levels)]
+                  + [(coords, "coords", None), (ii, "ii", None), (jj, "jj", None)])
+    if any(p.dtype != levels[0].dtype or p.dtype not in F16_OR_F32 for p in levels):
+        raise RuntimeError("altcorr_pyramid_forward: pyramid levels must all be float32 or all float16")
     if coords.dtype != torch.float32 or ii.dtype != torch.int64 or jj.dtype != torch.int64:
         raise RuntimeError("altcorr_pyramid_forward: coords must be float32 and ii/jj int64")
     frames, H, W, C = levels[0].shape
@@ -819,10 +709,8 @@ def altcorr_pyramid_forward(pyramid, coords, ii, jj, radius):
 def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
     """droid.cpp:205-217 -> altcorr_cuda_backward altcorr_kernel.cu:322-355 (fp32 only, like the reference)."""
     lib = _lib.load()
-    for x, n in ((fmap1, "fmap1"), (fmap2, "fmap2"), (coords, "coords"), (corr_grad, "corr_grad")):
-        _check_input(x, n)
-        if x.dtype != torch.float32:
-            raise RuntimeError(f"altcorr_backward: {n} must be float32")
+    check_tensors("altcorr_backward", [(fmap1, "fmap1", F32), (fmap2, "fmap2", F32), (coords, "coords", F32),
+                                       (corr_grad, "corr_grad", F32)])
     B, N, H, W, _ = coords.shape
     _, H1, W1, C = fmap1.shape
     _, H2, W2, _ = fmap2.shape

@@ -14,6 +14,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
+from ._args import _stream
 
 
 @dataclass
@@ -28,10 +29,6 @@ class BAProblemDev:
     eta: torch.Tensor         # [M_local,H,W]  rows = depth slots of THIS rank, ascending frame
     ii: torch.Tensor          # [E_local] int64
     jj: torch.Tensor          # [E_local] int64
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def read_status(lib, workspace):

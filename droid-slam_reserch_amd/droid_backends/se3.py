@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import _stream, check_tensors
 
 __all__ = ["SE3", "cat", "interpolate"]
 
@@ -17,24 +18,16 @@ INV, LOG, EXP, MATRIX = 0, 1, 2, 3   # DROID_SE3_*
 _WIDTH_OUT = {INV: 7, LOG: 6, EXP: 7, MATRIX: 16}
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _check_type(x, what, name, width):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a tensor, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"{what}: {name} must be float32, got {x.dtype}")
+    check_tensors(what, [(x, name, torch.float32)], placement=False)
     if x.dim() < 1 or x.shape[-1] != width:
         raise RuntimeError(f"{what}: {name} must be [..., {width}], got {tuple(x.shape)}")
 
 
 def _check(x, what, name, width):
-    """A caller's mistake is named before the device is looked at."""
+    """A caller's mistake is named before the device is looked at; records are made contiguous, not refused."""
     _check_type(x, what, name, width)
-    if not x.is_cuda:
-        raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
+    check_tensors(what, [(x, name, None)], types=False, contiguous=False)
 
 
 def _unary(x, op, what):
@@ -56,10 +49,7 @@ class SE3:
     def __init__(self, data):
         if isinstance(data, SE3):
             data = data.data
-        if not isinstance(data, torch.Tensor):
-            raise TypeError(f"SE3: data must be a tensor, got {type(data).__name__}")
-        if data.dtype != torch.float32:
-            raise RuntimeError(f"SE3: data must be float32, got {data.dtype}")
+        check_tensors("SE3", [(data, "data", torch.float32)], placement=False)
         if data.dim() < 1 or data.shape[-1] != 7:
             raise RuntimeError(f"SE3: data must be [..., 7] (tx ty tz qx qy qz qw), got {tuple(data.shape)}")
         self.data = data if data.is_contiguous() else data.contiguous()
@@ -173,14 +163,10 @@ def interpolate(poses, tstamp, n, query):
     _check_type(poses, what, "poses", 7)
     if not isinstance(tstamp, torch.Tensor) or tstamp.dtype != torch.float32:
         raise RuntimeError(f"{what}: tstamp must be a float32 tensor, got {getattr(tstamp, 'dtype', type(tstamp).__name__)}")
-    for x, name in ((poses, "poses"), (tstamp, "tstamp")):
-        if not x.is_cuda:
-            raise RuntimeError(f"{what}: {name} must be a HIP (cuda) tensor: droid_backends has no CPU path")
     if poses.dim() != 2 or tstamp.dim() != 1:
         raise RuntimeError(f"{what}: poses must be [buffer, 7] and tstamp [buffer], got {tuple(poses.shape)} and "
                            f"{tuple(tstamp.shape)}")
-    if tstamp.device != poses.device:
-        raise RuntimeError(f"{what}: tstamp is on {tstamp.device}, poses on {poses.device}")
+    check_tensors(what, [(poses, "poses", None), (tstamp, "tstamp", None)], types=False, contiguous=False, on=(poses, "poses"))
     n = int(n)
     if n < 1 or n > int(poses.shape[0]) or n > int(tstamp.shape[0]):
         raise RuntimeError(f"{what}: n = {n} must be at least 1 and at most the rows of poses and tstamp")

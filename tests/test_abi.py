@@ -23,6 +23,52 @@ def test_library_exports_every_declared_symbol(backends):
     assert sorted(backends._lib.SYMBOLS) == syms
 
 
+def _header_prototypes():
+    """{name: (result class, [parameter classes])} of every prototype in the header; classes are the words below."""
+    txt = open(os.path.join(ROOT, "include", "droid_backends_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+
+    def cls(decl, is_param):
+        if "*" in decl:
+            return "pointer"
+        words = decl.replace("const", " ").split()
+        words = words[:-1] if is_param else words   # a parameter ends with its name
+        assert len(words) == 1 and words[0] in ("int", "int64_t", "size_t", "float", "double"), decl
+        return words[0]
+
+    protos = {}
+    for res, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(droid_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in protos, name
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = (cls(res, False), [] if params == ["void"] else [cls(p, True) for p in params])
+    return protos
+
+
+def test_binding_table_matches_the_header_prototypes(backends):
+    """Arity, the class of every parameter and the class of the result of every function: a miscounted int or an
+    int64_t bound as int truncates silently at sizes no test reaches."""
+    protos = _header_prototypes()
+    syms = _header_symbols()
+    assert sorted(protos) == syms and len(protos) == len(syms) == 48   # a parser that skips a line must not pass
+    of_ctype = {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float",
+                ctypes.c_double: "double", ctypes.c_void_p: "pointer", ctypes.c_char_p: "pointer"}
+    assert len(of_ctype) == 7   # int64_t and size_t are distinct ctypes here
+
+    def cls(t):
+        return of_ctype.get(t) or ("pointer" if issubclass(t, ctypes._Pointer) else None)
+
+    assert sorted(backends._lib.ABI) == syms
+    lib = backends._lib.load()
+    for name, (res, params) in protos.items():
+        restype, argtypes = backends._lib.signature(name)
+        assert res in ("int", "size_t", "pointer"), name
+        assert cls(restype) == res, (name, restype, res)
+        assert [cls(a) for a in argtypes] == params, (name, argtypes, params)
+        fn = getattr(lib, name)   # and the loaded library carries exactly the table
+        assert fn.restype == restype and list(fn.argtypes) == argtypes, name
+
+
 def test_abi_version_and_workspace_query(backends):
     lib = backends._lib.load()
     assert lib.droid_abi_version() == 1
