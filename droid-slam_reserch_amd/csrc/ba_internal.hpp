@@ -109,6 +109,8 @@ struct BaView {
                            // Schur class 3}, written by ba_prep_kernel; nullptr: none.  hint_tag = tag of this workspace's last prepare
   int hint_tag;
   int* ov_ready;           // [block columns of the system] overlap mode: epoch of the last iteration whose reduced columns are in `sys`
+  float* pose_snap;        // [nbuf][7] the poses the iteration was linearised at: written by a spare workgroup of the depth-slot
+                           // linearisation launch, read by ba_backsub_kernel, whose last workgroup retracts the caller's tensor
 };
 
 // Launch geometry of one iteration.  ba_carve sizes buffers with these numbers and ba_launch_plan (below) turns them into
@@ -207,6 +209,7 @@ inline size_t ba_carve(BaView& v, void* ws, int E, int nbuf, int H, int W, int t
   v.ldiag = static_cast<double*>(take(sizeof(double) * chol_ldiag_doubles(v.n)));
   v.dx = static_cast<float*>(take(sizeof(float) * ((size_t)v.n + 8)));
   v.ov_ready = static_cast<int*>(take(sizeof(int) * ((size_t)(v.n + 1 + CHOL_NB - 1) / CHOL_NB + 8)));
+  v.pose_snap = static_cast<float*>(take(sizeof(float) * 7 * (size_t)nbuf));
   return off;
 }
 

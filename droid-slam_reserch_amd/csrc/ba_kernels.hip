@@ -187,7 +187,8 @@ __device__ __forceinline__ int s2_tiles(int nedges) {
 
 // Loads edges [x0, x0+cnt) of slot m (cnt <= SLOT_MAXE) by the first cnt threads of the workgroup.
 // ent_base = entry index of the first window edge of this chunk.  Ends with a barrier.
-template <typename S>
+// ENT = false: sm.ent is left alone (the back-substitution keeps its own flag there and has no use for the numbering).
+template <typename S, bool ENT = true>
 __device__ __forceinline__ void load_slot_meta(SlotMetaT<S>& sm, const BaView& v, const float* __restrict__ poses,
                                                const int64_t* __restrict__ jj, int f, int x0, int cnt,
                                                int ent_base) {
@@ -205,6 +206,7 @@ __device__ __forceinline__ void load_slot_meta(SlotMetaT<S>& sm, const BaView& v
     for (int n = 0; n < 3; n++) sm.T[t][9 + n] = T.t[n];
   }
   __syncthreads();
+  if (!ENT) return;
   if (t < cnt) {
     int a = ent_base;
     for (int u = 0; u < t; u++) a += (sm.pj[u] >= 0 && sm.pj[u] < v.P) ? 1 : 0;
@@ -459,6 +461,10 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     // assemble / Schur atomics and the solve touch) -- the linearisation is VALU bound, the stores ride along,
     // and the fill launch in front of it is gone
     if (blockIdx.y != 0 || blockIdx.z != 0) return;
+    // the last of them also leaves the poses of this iteration in the workspace: the back-substitution reads them there,
+    // because one workgroup of its launch retracts the caller's tensor in place (ba_backsub_kernel)
+    if (DEPTH && blockIdx.x == gridDim.x - 1)
+      for (int c = tid; c < 7 * v.nbuf; c += LIN_THREADS) v.pose_snap[c] = poses[c];
     const int nz = (int)gridDim.x - zero_base;
     if (v.packed) {
       double2* p = reinterpret_cast<double2*>(v.psys);
@@ -1865,19 +1871,73 @@ __global__ __launch_bounds__(256) void ba_syrk_fold_kernel(BaView v, int wgs1, i
   }
 }
 
+// The end of an iteration, in two parts that ba_backsub_kernel's last workgroup and ba_pose_retr_kernel share.
+// iteration_status (one thread): the status word and its host mirror; fl = the factorisation's failure word, 1 = not
+// positive definite (dx = 0 like dk:1202-1210), 2 = stalled grid.
+__device__ __forceinline__ void iteration_status(const BaView& v, int* __restrict__ status_mirror, int fl) {
+  const bool failed = fl != 0;
+  int st = v.hdr[HDR_STATUS];
+  if (failed) {
+    st |= (fl >= 2) ? STATUS_CHOL_STALL : STATUS_CHOL_FAIL;
+    atomicOr(&v.hdr[HDR_STATUS], (fl >= 2) ? STATUS_CHOL_STALL : STATUS_CHOL_FAIL);
+  }
+  if (status_mirror) {  // host-visible copy: the wrapper reads it at its next call without synchronising
+    __hip_atomic_store(status_mirror + 1, v.hdr[HDR_M], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(status_mirror, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // Errors are STICKY: words 2 / 3 count the iterations that ended with a contract violation or a stalled solve
+    // and OR their bits.  Only the device writes them (one kernel at a time per workspace), the host only reads
+    // and remembers the count it has reported, so a violation of call k survives call k+1 being enqueued (and
+    // resetting the workspace status) before the host looks.
+    if (st & (STATUS_BAD_INDEX | STATUS_ETA_ROWS | STATUS_CHOL_STALL)) {
+      const int cnt = __hip_atomic_load(status_mirror + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      const int bits = __hip_atomic_load(status_mirror + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(status_mirror + 3, bits | st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(status_mirror + 2, cnt + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+// pose_retr_one (one thread per window pose p < P): dx = fp32 of the fp64 solution, zeros when the factorisation
+// failed (:1202-1210), and the retraction T <- exp(dx) T (pose_retr_kernel :898-931)
+__device__ __forceinline__ void pose_retr_one(const BaView& v, float* __restrict__ poses, const double* __restrict__ xsol,
+                                              float* __restrict__ dx_out, bool failed, int p) {
+  const int k = v.t0 + p;
+  float xi[6], t[3], q[4], tn[3], qn[4];
+  for (int n = 0; n < 6; n++) {
+    xi[n] = failed ? 0.f : (float)xsol[6 * p + n];
+    v.dx[6 * p + n] = xi[n];
+    if (dx_out) dx_out[6 * p + n] = xi[n];
+  }
+  for (int n = 0; n < 3; n++) t[n] = poses[7 * k + n];
+  for (int n = 0; n < 4; n++) q[n] = poses[7 * k + 3 + n];
+  retr_se3(xi, t, q, tn, qn);
+  for (int n = 0; n < 3; n++) poses[7 * k + n] = tn[n];
+  for (int n = 0; n < 4; n++) poses[7 * k + 3 + n] = qn[n];
+}
+
 // ------------------------------------------------------------------------------------------
 // depth back-substitution + disparity retraction: dz = Q (w - sum_entries E^T dx), disps += dz
 // (EvT6x1_kernel :1095-1115 incl. its `p <= 0` early return, accum + :1417, disp_retr :933-946).
 // ------------------------------------------------------------------------------------------
 constexpr int BSUB_PPT = 1;  // pixels per thread: amortises the per-workgroup edge metadata
 
-__global__ __launch_bounds__(256) void ba_backsub_kernel(
-    BaView v, const float* __restrict__ poses, float* __restrict__ disps,
+// grid (slots + 1, pixel chunks).  The workgroup past the slots ends the iteration (iteration_status, pose_retr_one):
+// it retracts the caller's `poses` in place while the slots' workgroups, which start at any time, read the poses of
+// the linearisation from the workspace's snapshot -- the same values, and no launch boundary for 255 retractions.
+// Five waves per SIMD: 94 VGPRs, no scratch (4 waves at 106 VGPRs: 4.7 us slower, profiles/update_launch_ab.txt).
+__global__ __launch_bounds__(256, 5) void ba_backsub_kernel(
+    BaView v, float* __restrict__ poses, float* __restrict__ disps,
     const float* __restrict__ intrinsics, const float* __restrict__ weights,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const double* __restrict__ xsol,
-    float* __restrict__ dz_out) {
+    float* __restrict__ dx_out, float* __restrict__ dz_out, int* __restrict__ status_mirror) {
   __shared__ SlotMetaT<double> sm;     // fp64 relative poses: the E rows come from the point of the linearisation
   __shared__ float dxs[SLOT_MAXE][6];  // dx of each edge's target pose (0 when it does not feed back)
+  if (blockIdx.x == gridDim.x - 1) {
+    if (blockIdx.y != 0) return;
+    const int fl = v.hdr[HDR_CHOL_FAIL];
+    if (threadIdx.x == 0) iteration_status(v, status_mirror, fl);
+    for (int p = threadIdx.x; p < v.P; p += 256) pose_retr_one(v, poses, xsol, dx_out, fl != 0, p);
+    return;
+  }
   if ((int)blockIdx.x >= min(v.hdr[HDR_M], v.M)) return;
   const int m = v.order[blockIdx.x];
   const int HW = v.HW;
@@ -1911,7 +1971,7 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
   for (int c0 = 0; c0 < nedges; c0 += SLOT_MAXE) {
     const int cnt = min(SLOT_MAXE, nedges - c0);
     if (c0 > 0) __syncthreads();
-    load_slot_meta(sm, v, poses, jj, f, x_beg + c0, cnt, 0);
+    load_slot_meta<double, false>(sm, v, v.pose_snap, jj, f, x_beg + c0, cnt, 0);
     if (threadIdx.x < cnt) {
       const int pj = sm.pj[threadIdx.x];
       const bool on = pj > 0 && pj < v.P;  // entries with p <= 0 or p >= P do not feed back
@@ -1982,47 +2042,14 @@ __global__ __launch_bounds__(256) void ba_backsub_kernel(
   }
 }
 
-// pose retraction T <- exp(dx) T for the window (pose_retr_kernel :898-931); dx = fp32 of the fp64
-// solution, zeros when the factorisation failed (:1202-1210)
+// the end of an iteration without depth slots (motion-only): one thread per window pose
 __global__ void ba_pose_retr_kernel(BaView v, float* __restrict__ poses, const double* __restrict__ xsol,
                                     float* __restrict__ dx_out, int* __restrict__ status_mirror) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int fl = v.hdr[HDR_CHOL_FAIL];  // 1 = not positive definite (dx = 0 like dk:1202-1210), 2 = stalled grid
-  const bool failed = fl != 0;
-  if (p == 0) {
-    int st = v.hdr[HDR_STATUS];
-    if (failed) {
-      st |= (fl >= 2) ? STATUS_CHOL_STALL : STATUS_CHOL_FAIL;
-      atomicOr(&v.hdr[HDR_STATUS], (fl >= 2) ? STATUS_CHOL_STALL : STATUS_CHOL_FAIL);
-    }
-    if (status_mirror) {  // host-visible copy: the wrapper reads it at its next call without synchronising
-      __hip_atomic_store(status_mirror + 1, v.hdr[HDR_M], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(status_mirror, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      // Errors are STICKY: words 2 / 3 count the iterations that ended with a contract violation or a stalled solve
-      // and OR their bits.  Only the device writes them (one kernel at a time per workspace), the host only reads
-      // and remembers the count it has reported, so a violation of call k survives call k+1 being enqueued (and
-      // resetting the workspace status) before the host looks.
-      if (st & (STATUS_BAD_INDEX | STATUS_ETA_ROWS | STATUS_CHOL_STALL)) {
-        const int cnt = __hip_atomic_load(status_mirror + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        const int bits = __hip_atomic_load(status_mirror + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(status_mirror + 3, bits | st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(status_mirror + 2, cnt + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  const int fl = v.hdr[HDR_CHOL_FAIL];
+  if (p == 0) iteration_status(v, status_mirror, fl);
   if (p >= v.P) return;
-  const int k = v.t0 + p;
-  float xi[6], t[3], q[4], tn[3], qn[4];
-  for (int n = 0; n < 6; n++) {
-    xi[n] = failed ? 0.f : (float)xsol[6 * p + n];
-    v.dx[6 * p + n] = xi[n];
-    if (dx_out) dx_out[6 * p + n] = xi[n];
-  }
-  for (int n = 0; n < 3; n++) t[n] = poses[7 * k + n];
-  for (int n = 0; n < 4; n++) q[n] = poses[7 * k + 3 + n];
-  retr_se3(xi, t, q, tn, qn);
-  for (int n = 0; n < 3; n++) poses[7 * k + n] = tn[n];
-  for (int n = 0; n < 4; n++) poses[7 * k + 3 + n] = qn[n];
+  pose_retr_one(v, poses, xsol, dx_out, fl != 0, p);
 }
 
 // multi-GPU: psys (packed block-column major, all-reduced over the ranks) -> sys (pitched, what the solver factors in
@@ -2151,9 +2178,10 @@ void launch_update(const BaView& v, float* poses, float* disps, const float* int
                    const int64_t* ii, const int64_t* jj, const double* x, float* dx_out, float* dz_out,
                    bool motion_only, hipStream_t s, int* status_mirror) {
   if (!motion_only && v.M > 0)
-    hipLaunchKernelGGL(ba_backsub_kernel, dim3(v.M, (v.HW + 256 * BSUB_PPT - 1) / (256 * BSUB_PPT)), dim3(256), 0, s, v, poses, disps,
-                       intr, weights, ii, jj, x, dz_out);
-  hipLaunchKernelGGL(ba_pose_retr_kernel, dim3((v.P + 63) / 64), dim3(64), 0, s, v, poses, x, dx_out, status_mirror);
+    hipLaunchKernelGGL(ba_backsub_kernel, dim3(v.M + 1, (v.HW + 256 * BSUB_PPT - 1) / (256 * BSUB_PPT)), dim3(256), 0, s, v, poses, disps,
+                       intr, weights, ii, jj, x, dx_out, dz_out, status_mirror);
+  else  // no depth slots: the end of the iteration has a launch of its own
+    hipLaunchKernelGGL(ba_pose_retr_kernel, dim3((v.P + 63) / 64), dim3(64), 0, s, v, poses, x, dx_out, status_mirror);
 }
 
 }  // namespace droid
