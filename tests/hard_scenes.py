@@ -22,7 +22,6 @@ Bars (`bars`): nothing in them is measured from the device.
          fp64 finish).
 """
 import copy
-import functools
 
 import numpy as np
 
@@ -132,6 +131,7 @@ class Scene:
         self.id, self._make, self.family, self.classes, self.packed = id, make, family, classes, packed
         self.motion_only = classes == {"motion"}
         self._p = None
+        self._bars = None
 
     def problem(self):
         if self._p is None:
@@ -185,12 +185,13 @@ def build64(oracle, p, motion_only):
     return ph, H, b
 
 
-@functools.lru_cache(maxsize=None)
-def bars(scene_id):
-    """The bars of scene `scene_id` (see the head of this file), from the oracle alone, computed once.  Next to H, b,
-    dx, state: e32 (H, b, state of the float32 oracle), cond, n, and `ref`: the fp64 system and its finish."""
+def scene_bars(sc):
+    """The bars of the scene `sc` (see the head of this file; any object with id, family, motion_only and problem()),
+    from the oracle alone, computed once per scene object.  Next to H, b, dx, state: e32 (H, b, state of the float32
+    oracle), cond, n, and `ref`: the fp64 system and its finish."""
+    if getattr(sc, "_bars", None) is not None:
+        return sc._bars
     import oracle
-    sc = SCENES[scene_id]
     p, mo = sc.problem(), sc.motion_only
     ph64, Ho, bo = build64(oracle, p, mo)
     ph32 = oracle.BAPhases("f32")
@@ -204,12 +205,22 @@ def bars(scene_id):
     s32 = ph32.finish(full, bo, lm, ep)
     e32s = relative_state_error(p, s32[:2], s64[:2])
     fam = STAGE_BARS[sc.family]
-    return dict(H=max(fam["H"], 2 * e32["H"]), b=max(fam["b"], 2 * e32["b"]), dx=2.0 ** -23 + 10 * n * 2.0 ** -53 * cond,
-                state=max(fam["state"], 2 * max(e32s)), e32=dict(H=e32["H"], b=e32["b"], state=e32s, dead=e32["dead"]),
-                cond=cond, n=n, ref=dict(H=Ho, b=bo, A=A, poses=s64[0], disps=s64[1], dx=s64[2]))
+    sc._bars = dict(H=max(fam["H"], 2 * e32["H"]), b=max(fam["b"], 2 * e32["b"]), dx=2.0 ** -23 + 10 * n * 2.0 ** -53 * cond,
+                    state=max(fam["state"], 2 * max(e32s)), e32=dict(H=e32["H"], b=e32["b"], state=e32s, dead=e32["dead"]),
+                    cond=cond, n=n, ref=dict(H=Ho, b=bo, A=A, poses=s64[0], disps=s64[1], dx=s64[2]))
+    return sc._bars
+
+
+def bars(scene_id):
+    """scene_bars of the scene of SCENES with that id"""
+    return scene_bars(SCENES[scene_id])
+
+
+def scene_bars_line(sc):
+    b = scene_bars(sc)
+    return (f"[{sc.id}] bars H {b['H']:.2e} b {b['b']:.2e} dx {b['dx']:.2e} state {b['state']:.2e} | float32 oracle H "
+            f"{b['e32']['H']:.2e} b {b['e32']['b']:.2e} state {max(b['e32']['state']):.2e} | n {b['n']} cond {b['cond']:.2e}")
 
 
 def bars_line(scene_id):
-    b = bars(scene_id)
-    return (f"[{scene_id}] bars H {b['H']:.2e} b {b['b']:.2e} dx {b['dx']:.2e} state {b['state']:.2e} | float32 oracle H "
-            f"{b['e32']['H']:.2e} b {b['e32']['b']:.2e} state {max(b['e32']['state']):.2e} | n {b['n']} cond {b['cond']:.2e}")
+    return scene_bars_line(SCENES[scene_id])

@@ -21,7 +21,7 @@ def test_header_word_indices_match_ba_internal():
     assert m, "enum HDR_* not found"
     body = re.sub(r"//[^\n]*", "", m.group(1))
     words = {k: int(v) for k, v in re.findall(r"(HDR_\w+)\s*=\s*(\d+)", body)}
-    for name in ("HDR_M", "HDR_NC1", "HDR_NC2"):
+    for name in ("HDR_M", "HDR_NENT", "HDR_NC1", "HDR_NC2"):
         assert getattr(util, name) == words[name], (name, getattr(util, name), words[name])
 
 

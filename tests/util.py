@@ -120,9 +120,9 @@ def assert_composite_parity(hip, ref, tol, tag="", sensitive=None, hard=2e-3):
 
 # ---- stage-by-stage parity of one Gauss-Newton iteration (tests/test_gpu_ba_stages.py) ------------------------------
 # Words of the workspace header (csrc/ba_internal.hpp: enum HDR_*, the first thing ba_carve places in the workspace):
-# depth slots, and the slots served by the two SYRK instances (Schur classes 1 and 2).  tests/test_stage_checker.py
-# parses the enum so that these stay equal to it.
-HDR_M, HDR_NC1, HDR_NC2 = 1, 5, 6
+# depth slots, Schur entries of all slots, and the slots served by the two SYRK instances (Schur classes 1 and 2).
+# tests/test_stage_checker.py parses the enum so that these stay equal to it.
+HDR_M, HDR_NENT, HDR_NC1, HDR_NC2 = 1, 3, 5, 6
 
 # Bars per graph family (tests/stage_graphs.py), set from the errors measured on the MI355X (DESIGN.md section 5,
 # "stage by stage"), at most 4x the worst of them:
