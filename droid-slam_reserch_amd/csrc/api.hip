@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/droid_backends_hip.h"
+#include "../../include/droid_update_hip.h"
 #include "ba_internal.hpp"
 #include "graph.hpp"
 #include "launchers.hpp"
@@ -808,6 +809,92 @@ int droid_point_cloud(const float* poses, const float* disps, const float* intri
   launch_point_cloud(poses, disps, intrinsics, index, thresh, images, n, nbuf, H, W, min_count, disp_ratio, points, colors,
                      src, offsets, matrices, workspace, (hipStream_t)stream);
   return check_hip("point_cloud");
+}
+
+
+// ---- the BA inputs of a factor-graph update (ba_inputs.hip, include/droid_update_hip.h) -------------------------
+// sizes droid_ba_inputs and its workspace query check; <0 after fail()
+static int ba_inputs_check(int E, int Ei, int nbuf) {
+  if (E < 1) return fail(DROID_E_ARG, "ba_inputs: bad %s", "E (at least 1)");
+  if (Ei < 0) return fail(DROID_E_ARG, "ba_inputs: bad %s", "Ei (negative)");
+  if ((int64_t)E + Ei > 65535) return fail(DROID_E_ARG, "ba_inputs: bad %s", "E + Ei (at most 65535)");
+  if (nbuf < 1 || nbuf > DROID_BA_INPUTS_MAX_NBUF)
+    return fail(DROID_E_ARG, "ba_inputs: bad %s", "nbuf (1 .. 16384: the prepare launch's tables live in LDS)");
+  return 0;
+}
+
+size_t droid_ba_inputs_workspace_bytes(int E, int Ei, int nbuf) {
+  if (ba_inputs_check(E, Ei, nbuf)) return 0;
+  return ba_inputs_workspace_bytes(E, Ei, nbuf);
+}
+
+int droid_ba_inputs(const int64_t* ii, const int64_t* jj, const float* a, const void* delta, const void* w,
+                    const void* damping_net, float* damping_buf, const int64_t* ii_inac, const int64_t* jj_inac,
+                    const float* target_inac, const float* weight_inac, int E, int Ei, int H, int W, int nbuf,
+                    int n_damp, int net_dtype, int damp_dtype, int t0, float ep, float* target_state,
+                    float* weight_state, int64_t* ii_ba, int64_t* jj_ba, float* target_ba, float* weight_ba, int cap_e,
+                    float* eta, int64_t* frames_active, int64_t* frames_eta, int cap_m, int* info, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  int rc = ba_inputs_check(E, Ei, nbuf);
+  if (rc) return rc;
+  if (H < 1 || W < 1) return fail(DROID_E_ARG, "ba_inputs: bad %s", "map size (H, W >= 1)");
+  const unsigned __int128 hw = (unsigned __int128)H * W, lim = (unsigned __int128)1 << 62;
+  if ((unsigned)(E + Ei) * hw * 2 > lim)
+    return fail(DROID_E_ARG, "ba_inputs: %s", "(E + Ei) * H * W * 2 exceeds the kernel's index range (2^62)");
+  const int rows = E + Ei, mcap = nbuf < rows ? nbuf : rows;
+  if (cap_e < rows) return fail(DROID_E_ARG, "ba_inputs: bad %s", "cap_e (below E + Ei)");
+  if (cap_m < mcap) return fail(DROID_E_ARG, "ba_inputs: bad %s", "cap_m (below min(nbuf, E + Ei))");
+  if (damping_net && n_damp < 0) return fail(DROID_E_ARG, "ba_inputs: bad %s", "n_damp (negative)");
+  if (t0 < -1) return fail(DROID_E_ARG, "ba_inputs: bad %s", "t0 (>= 0, or -1 for none)");
+  if (net_dtype != DROID_F16 && net_dtype != DROID_F32) return fail(DROID_E_ARG, "ba_inputs: bad %s", "net_dtype (f16 or f32)");
+  if (damp_dtype != DROID_F16 && damp_dtype != DROID_F32) return fail(DROID_E_ARG, "ba_inputs: bad %s", "damp_dtype (f16 or f32)");
+  if (!ii || !jj || !a || !w || !damping_buf)
+    return fail(DROID_E_ARG, "ba_inputs: null %s", "pointer (ii / jj / a / w / damping_buf)");
+  if (Ei > 0 && (!ii_inac || !jj_inac || !target_inac || !weight_inac))
+    return fail(DROID_E_ARG, "ba_inputs: null %s", "pointer (ii_inac / jj_inac / target_inac / weight_inac) with Ei > 0");
+  if (!ii_ba || !jj_ba || !target_ba || !weight_ba || !eta || !frames_active || !frames_eta || !info)
+    return fail(DROID_E_ARG, "ba_inputs: null %s",
+                "pointer (ii_ba / jj_ba / target_ba / weight_ba / eta / frames_active / frames_eta / info)");
+  if (!delta && (target_state || weight_state))
+    return fail(DROID_E_ARG, "ba_inputs: %s", "target_state / weight_state given in emit-only mode (delta is NULL)");
+  if (!workspace) return fail(DROID_E_ARG, "ba_inputs: null %s", "workspace");
+  const size_t ws_need = ba_inputs_workspace_bytes(E, Ei, nbuf);
+  if (workspace_bytes < ws_need) return fail(DROID_E_WORKSPACE, "ba_inputs: %s", "workspace too small");
+  if ((uintptr_t)workspace % 4 != 0) return fail(DROID_E_ARG, "ba_inputs: %s", "workspace is not 4-byte aligned");
+
+  // bytes of n rows of `per` elements of `size` bytes, saturating
+  auto bytes = [](uint64_t n, unsigned __int128 per, unsigned size) -> uint64_t {
+    const unsigned __int128 b = n * per * size;
+    return b > UINT64_MAX ? UINT64_MAX : (uint64_t)b;
+  };
+  const unsigned net_size = delta ? (net_dtype == DROID_F16 ? 2 : 4) : 4, damp_size = damp_dtype == DROID_F16 ? 2 : 4;
+  struct Range { const void* p; uint64_t bytes; const char* name; };
+  const Range ins[11] = {{ii, bytes(E, 1, 8), "ii"}, {jj, bytes(E, 1, 8), "jj"}, {a, bytes(E, hw * 2, 4), "a"},
+                         {delta, delta ? bytes(E, hw * 2, net_size) : 0, "delta"}, {w, bytes(E, hw * 2, net_size), "w"},
+                         {damping_net, damping_net ? bytes(n_damp, hw, damp_size) : 0, "damping_net"},
+                         {ii_inac, bytes(Ei, 1, 8), "ii_inac"}, {jj_inac, bytes(Ei, 1, 8), "jj_inac"},
+                         {target_inac, bytes(Ei, hw * 2, 4), "target_inac"}, {weight_inac, bytes(Ei, hw * 2, 4), "weight_inac"},
+                         {nullptr, 0, ""}};
+  const Range outs[12] = {{damping_buf, bytes(nbuf, hw, 4), "damping_buf"},
+                          {target_state, target_state ? bytes(E, hw * 2, 4) : 0, "target_state"},
+                          {weight_state, weight_state ? bytes(E, hw * 2, 4) : 0, "weight_state"},
+                          {ii_ba, bytes(cap_e, 1, 8), "ii_ba"}, {jj_ba, bytes(cap_e, 1, 8), "jj_ba"},
+                          {target_ba, bytes(cap_e, hw * 2, 4), "target_ba"}, {weight_ba, bytes(cap_e, hw * 2, 4), "weight_ba"},
+                          {eta, bytes(cap_m, hw, 4), "eta"}, {frames_active, bytes(cap_m, 1, 8), "frames_active"},
+                          {frames_eta, bytes(cap_m, 1, 8), "frames_eta"}, {info, 32, "info"}, {workspace, ws_need, "workspace"}};
+  for (int o = 0; o < 12; o++) {
+    const Range& out = outs[o];
+    for (const Range& in : ins)
+      if (bytes_overlap(out.p, out.bytes, in.p, in.bytes)) return fail(DROID_E_ARG, "ba_inputs: %s overlaps %s", out.name, in.name);
+    for (int q = 0; q < o; q++)
+      if (bytes_overlap(out.p, out.bytes, outs[q].p, outs[q].bytes))
+        return fail(DROID_E_ARG, "ba_inputs: %s overlaps %s", out.name, outs[q].name);
+  }
+  BaInputsArgs x{ii, jj, a, delta, w, damping_net, damping_buf, ii_inac, jj_inac, target_inac, weight_inac, E, Ei, H, W, nbuf,
+                 damping_net ? n_damp : 0, net_dtype == DROID_F16, damp_dtype == DROID_F16, t0, ep, target_state, weight_state,
+                 ii_ba, jj_ba, target_ba, weight_ba, eta, frames_active, frames_eta, info, workspace};
+  launch_ba_inputs(x, (hipStream_t)stream);
+  return check_hip("ba_inputs");
 }
 
 }  // extern "C"

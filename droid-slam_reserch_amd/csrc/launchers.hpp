@@ -53,6 +53,27 @@ void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask,
 size_t graph_mean_workspace_bytes(int E, int range);
 void launch_graph_mean(const void* src, const int64_t* index, void* out, int E, int64_t plane, int M, int range,
                        int compact, bool half, int* groups_out, void* workspace, hipStream_t s);
+// ba_inputs.hip (include/droid_update_hip.h: the arguments of droid_ba_inputs under their names there)
+struct BaInputsArgs {
+  const int64_t *ii, *jj;
+  const float* a;
+  const void *delta, *w, *damping_net;
+  float* damping_buf;
+  const int64_t *ii_inac, *jj_inac;
+  const float *target_inac, *weight_inac;
+  int E, Ei, H, W, nbuf, n_damp;
+  bool net_half, damp_half;
+  int t0;
+  float ep;
+  float *target_state, *weight_state;
+  int64_t *ii_ba, *jj_ba;
+  float *target_ba, *weight_ba, *eta;
+  int64_t *frames_active, *frames_eta;
+  int* info;
+  void* workspace;
+};
+size_t ba_inputs_workspace_bytes(int E, int Ei, int nbuf);
+void launch_ba_inputs(const BaInputsArgs& x, hipStream_t s);
 // se3_ops.hip
 void launch_se3_unary(const float* in, float* out, int64_t n, int op, hipStream_t s);
 void launch_se3_mul(const float* a, int stride_a, const float* b, int stride_b, float* out, int64_t n, hipStream_t s);

@@ -68,14 +68,21 @@ ABI = {
     "droid_test_wave_reduce32": ("i", "3p"),
 }
 SYMBOLS = list(ABI)   # tests check that the library exports them all and the header declares no other
+# The second header, include/droid_update_hip.h, in the same notation (tests/test_ba_inputs_abi.py holds it against the
+# prototypes there).  The same library exports these; load() binds both tables.
+ABI_UPDATE = {
+    "droid_ba_inputs_workspace_bytes": ("z", "3i"),
+    "droid_ba_inputs": ("i", "11p 9i f 6p i 3p i 2p z p"),
+}
+SYMBOLS_UPDATE = list(ABI_UPDATE)
 _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
           "p": ctypes.c_void_p, "P": ctypes.POINTER(ctypes.c_void_p), "I": ctypes.POINTER(ctypes.c_int),
           "Z": ctypes.POINTER(ctypes.c_size_t), "s": ctypes.c_char_p}
 
 
 def signature(name):
-    """(restype, argtypes) of an ABI entry as ctypes types."""
-    res, args = ABI[name]
+    """(restype, argtypes) of an entry of ABI or ABI_UPDATE as ctypes types."""
+    res, args = ABI[name] if name in ABI else ABI_UPDATE[name]
     return _CTYPE[res], [_CTYPE[run[-1]] for run in args.split() for _ in range(int(run[:-1] or 1))]
 
 
@@ -99,7 +106,7 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:
+    for s in SYMBOLS + SYMBOLS_UPDATE:
         if not hasattr(lib, s):
             raise DroidBackendError(f"{LIB_PATH} does not export {s}")
         fn = getattr(lib, s)

@@ -15,6 +15,9 @@
  *   poses  [nbuf,7]  f32  (tx ty tz qx qy qz qw), world->camera     depth_video.py:33
  *   disps  [nbuf,H,W] f32 ; disps_sens [nbuf,H,W] f32 ; intrinsics [4] f32 (fx fy cx cy)
  *   targets, weights [E,2,H,W] f32 ; eta [M,H,W] f32 ; ii, jj [E] int64
+ *
+ * A second header, droid_update_hip.h, declares the operators between the update network and `ba` (the BA inputs of a
+ * factor-graph update) with the same conventions; the same library exports them.
  */
 #ifndef DROID_BACKENDS_HIP_H
 #define DROID_BACKENDS_HIP_H
