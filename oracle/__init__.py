@@ -4,12 +4,23 @@ TEST INFRASTRUCTURE ONLY.  Only ``tests/``, ``__graft_entry__.smoke()`` and the 
 leg of ``bench.py`` may import this package, and only as the checker / timed CPU baseline.  The
 product (``droid-slam_reserch_amd``) never imports it and fails loudly without its HIP library.
 
-PARITY UNPINNED: the reference (/root/reference) holds no tests, fixtures or golden vectors for
-this path, its CUDA extension cannot be compiled here (no nvcc, no Eigen) and its Python twin
-needs the un-vendored ``lietorch``/``torch_scatter``.  The restatement is
-therefore pinned by independent derivations (autograd/finite-difference Jacobians, a dense
-normal-equation solve, bilinear sampling identities) in ``tests/test_oracle_*.py`` -- not by
-outputs of the reference itself.
+PARITY: PINNED TO THE REFERENCE'S PYTHON PROGRAMS, where it has them.  The reference holds no tests or
+fixtures and its CUDA extension cannot be compiled here (no nvcc, no Eigen), but its second implementation
+in plain PyTorch (geom/projective_ops.py, geom/ba.py + geom/chol.py, modules/corr.py, droid_net.py) runs
+unchanged on the CPU in float64 over small stand-ins for ``lietorch``/``torch_scatter`` (tests/refshim/,
+tests/reference_programs.py).  Its outputs are committed (tests/golden/reference_*.npz) and
+tests/test_reference_pin.py holds this package to them; tests/test_gpu_reference_pin.py holds the device to
+them directly.
+  Pinned: projection, its Jacobians and the MIN_DEPTH rule; the per-edge blocks and their scatter; C, w and
+  the reduced system; the motion-only system; the all-pairs volume and both pyramids; convex upsampling.
+  Still unpinned: lietorch itself (a stand-in; the reference ran on quaternions normalised in float64, since
+  off the unit sphere the group operations are not pinned by anything); the CUDA-only programs (correlation
+  lookups, frame_distance, depth_filter, Eigen's solve); stereo pose blocks; the disps_sens / alpha term,
+  which geom/ba.py does not have.  There the independent derivations of ``tests/test_oracle_*.py``
+  (autograd / finite-difference Jacobians, a dense normal-equation solve, bilinear sampling identities)
+  remain the only pin.
+  Where the two programs of the reference disagree this package follows the CUDA one:
+  damping on the Schur diagonal, the first window pose left out of the back-substitution, MIN_DEPTH 0.25.
 
 * ``ba_oracle.c`` / ``ba_oracle_impl.h``: plain-C restatement of ``src/droid_kernels.cu``
   (``ba``, ``frame_distance``, ``projmap``, ``iproj``), fp64 ("truth") and fp32 variants.

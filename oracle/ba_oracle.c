@@ -1,7 +1,7 @@
 /*
  * oracle/ba_oracle.c -- builds the two precisions of the BA restatement (see ba_oracle_impl.h).
  * TEST INFRASTRUCTURE ONLY (checker + timed CPU baseline); never on the product path.
- * PARITY UNPINNED: see the header of ba_oracle_impl.h.
+ * PARITY: see the header of ba_oracle_impl.h.
  *
  *   gcc -O2 -fopenmp -shared -fPIC ba_oracle.c -o libdroid_oracle.so -lm      (oracle/Makefile)
  */

@@ -3,10 +3,12 @@
  *
  * TEST INFRASTRUCTURE ONLY.  Nothing under oracle/ is part of the product path; only tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it, and there only as the
- * checker / timed CPU baseline.  PARITY UNPINNED: the reference ships no fixtures or tests for
- * this path and neither its CUDA extension nor its lietorch-based Python twin can run in this
- * pipeline, so this restatement is pinned only by independent derivations
- * (tests/test_oracle_*.py), not by reference outputs.
+ * checker / timed CPU baseline.  PARITY: the linearisation, the scatter, C, w and the reduced and
+ * motion-only systems are pinned to outputs of the reference's Python twin (geom/ba.py, run over
+ * stand-ins for lietorch / torch_scatter: tests/test_reference_pin.py); where the twin differs from
+ * the CUDA code restated here (damping placement, the first window pose in the back-substitution,
+ * MIN_DEPTH) the CUDA rule stands.  The solve, stereo pose blocks and the sensor-depth term are
+ * pinned only by independent derivations (tests/test_oracle_*.py).
  *
  * The file is included twice by ba_oracle.c, once with REAL=double (suffix _f64, "truth": every
  * quantity in double) and once with REAL=float (suffix _f32: fp32 wherever the reference's device

@@ -1,5 +1,5 @@
 """numpy restatement of the reference's correlation lookups.  TEST INFRASTRUCTURE ONLY
-(see oracle/__init__.py; PARITY UNPINNED -- no reference fixtures exist for this path).
+(see oracle/__init__.py; parity unpinned -- the lookups are CUDA-only programs of the reference, no fixtures exist).
 
 * corr_index_forward follows /root/reference/src/correlation_kernels.cu:19-70 (kernel) and
   :126-155 (wrapper: output zero-initialised, dtype of the volume).

@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE ONLY (see oracle/__init__.py): numpy fp64 restatement of the Python-side reprojection and
 motion features of the update step, and of the geometry operators of src/droid_kernels.cu together with the
-quantity each of their DECISIONS is taken on.  **parity unpinned**: lietorch is not importable here, so this follows
-the reference's formulas by reading, and is pinned only by closed-form cases and by the C restatement
-(tests/test_oracle_geom.py).
+quantity each of their DECISIONS is taken on.  `reproject` is pinned to outputs of the reference's own
+projective_transform (tests/test_reference_pin.py, over a stand-in for lietorch, which itself stays unpinned); the
+operators of src/droid_kernels.cu only by closed-form cases and by the C restatement (tests/test_oracle_geom.py).
 
   reproject            droid_slam/depth_video.py:150-158 -> droid_slam/geom/projective_ops.py:96-125
   iproj / actp / proj  droid_slam/geom/projective_ops.py:18-37, :75-93 (X1 = Gij * X0), :39-51
