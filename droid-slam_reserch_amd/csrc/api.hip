@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/droid_backends_hip.h"
+#include "../../include/droid_test_hooks_hip.h"
 #include "../../include/droid_update_hip.h"
 #include "ba_internal.hpp"
 #include "graph.hpp"
@@ -531,6 +532,36 @@ int droid_test_wave_reduce32(const float* in, float* out, void* stream) {
   if (!in || !out) return fail(DROID_E_ARG, "test_wave_reduce32: null %s", "pointer");
   launch_wave_reduce32_test(in, out, (hipStream_t)stream);
   return check_hip("test_wave_reduce32");
+}
+
+int droid_test_ba_lin(const float* poses, const float* disps, const float* intrinsics, const float* disps_sens,
+                      const float* targets, const float* weights, const float* eta, const int64_t* ii, const int64_t* jj,
+                      int E, int nbuf, int H, int W, int M, int t0, int t1, int motion_only, int ragged, void* workspace,
+                      size_t workspace_bytes, float* hpart_out, float* q_out, float* w_out, float* ebuf_out,
+                      size_t* words_out, void* stream) {
+  const BaDims d{E, nbuf, H, W, M, t0, t1, motion_only};
+  BaView v;
+  if (int rc = ba_view(v, workspace, workspace_bytes, d)) return rc;
+  if (!poses || !disps || !intrinsics) return fail(DROID_E_ARG, "test_ba_lin: null %s", "state pointer");
+  if (E > 0 && (!targets || !weights || !ii || !jj)) return fail(DROID_E_ARG, "test_ba_lin: null %s", "edge data");
+  if (!motion_only && v.M > 0 && (!eta || !disps_sens)) return fail(DROID_E_ARG, "test_ba_lin: null %s", "eta/disps_sens");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t words[4] = {(size_t)E * v.nch * LIN_WAVES * 32, (size_t)v.M * v.HW, (size_t)v.M * v.HW,
+                           v.wide ? 6 * ((size_t)v.M + E) * v.HW : 0};
+  const float* src[4] = {v.Hpart, v.Q, v.w, v.Ebuf};
+  float* dst[4] = {hpart_out, q_out, w_out, ebuf_out};
+  if (dst[0] || dst[1] || dst[2] || dst[3])   // (no output buffer: a size query, nothing is launched)
+    launch_lin_test(v, poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, motion_only != 0, ragged != 0, s);
+  if (words_out) {   // and the host's choice of instantiation (ba_carve)
+    words_out[4] = (size_t)v.wide;
+    words_out[5] = (size_t)v.zsplit;
+  }
+  for (int k = 0; k < 4; k++) {
+    if (words_out) words_out[k] = words[k];
+    if (dst[k] && words[k])
+      (void)hipMemcpyAsync(dst[k], src[k], sizeof(float) * words[k], hipMemcpyDeviceToDevice, s);
+  }
+  return check_hip("test_ba_lin");
 }
 
 size_t droid_chol_scratch_doubles(int n) { return CholSystem::scratch_doubles(n); }

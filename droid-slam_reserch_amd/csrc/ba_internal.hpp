@@ -263,6 +263,11 @@ struct CholSystem {
 // kernels' launchers (ba_kernels.hip / chol.hip)
 // one wave through the linearisation's wave_reduce32: in [64][32] (lane, value) -> out [64] (what each lane returns)
 void launch_wave_reduce32_test(const float* in, float* out, hipStream_t s);
+// the linearisation (stage 0 of launch_build_stage) of a prepared workspace alone; ragged: with the per-lane guarded
+// body of ba_lin_kernel also where the pixel count is a multiple of the chunk and the product runs the FULL body
+void launch_lin_test(const BaView& v, const float* poses, const float* disps, const float* intr, const float* sens,
+                     const float* targets, const float* weights, const float* eta, const int64_t* ii, const int64_t* jj,
+                     bool motion_only, bool ragged, hipStream_t s);
 void launch_prep(const BaView& v, const int64_t* ii, const int64_t* jj, hipStream_t s);
 // multi-GPU: expand the (all-reduced) packed system into the pitched matrix the solver factors in place
 void launch_unpack_system(const BaView& v, hipStream_t s);

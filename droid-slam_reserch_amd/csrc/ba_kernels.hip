@@ -433,6 +433,138 @@ __global__ __launch_bounds__(1024) void ba_prep_kernel(BaView vg, const int64_t*
 }
 
 // ------------------------------------------------------------------------------------------
+// The per-pixel arithmetic of the linearisation's FULL body (ba_lin_kernel below), roundings pinned in source.
+//
+// The ragged body leaves the choice of which a*b + c to fuse to the compiler, and that choice depends on the basic block:
+// inside one pixel's block the SLP vectoriser packs u/v rows and may swap the operands of a sum of two products before the
+// backend contracts one of them, so pixel 0 and pixel 1 of a lane, and the instantiations with and without E rows, fuse
+// different products.  The FULL body runs both pixels of a lane in ONE block with no test per pixel row -- no half-used
+// packed operations and the register shuffles around them, the two pixels' fp64 division chains interleaved, 123 instead of
+// 156 VGPRs and a fourth wave per SIMD in the headline's instantiation (profiles/lin_pinned_ab.txt; the vectoriser pairs
+// little across the pixels, the body is mostly scalar) -- and must round like the ragged body all the same.  So
+// contraction is off in everything below and every fused multiply-add the ragged body's ISA has is an explicit fma here,
+// every separate multiply and add a plain operator; where an operation is packed, each half rounds like its scalar form.  The
+// pattern was read from the ragged instantiations' instruction selection (hipcc -O3 --offload-arch=gfx950); the test
+// tests/test_gpu_lin_pinned.py holds FULL against the ragged body bit for bit (droid_test_ba_lin forces the latter).
+// Nothing here is shared with another kernel: the helpers of se3.hpp and their contraction stay as they are.
+// ------------------------------------------------------------------------------------------
+// a*b + c*d, rounded as ...
+enum { LIN_FUSE_AB = 0,     // fma(a, b, c*d)
+       LIN_FUSE_CD = 1,     // fma(c, d, a*b)
+       LIN_FUSE_NONE = 2 }; // a*b + c*d
+__device__ __forceinline__ float lin_sum2(int how, float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  return how == LIN_FUSE_AB ? fmaf(a, b, c * d) : (how == LIN_FUSE_CD ? fmaf(c, d, a * b) : a * b + c * d);
+}
+// How pixel p of a lane rounds its sums of two products (u-row product first, as the ragged body writes them).  Every
+// `how` below is a compile-time constant once the loops over pixels and block entries are unrolled.
+struct LinFuse {
+  uint32_t cd;    // bit l: Hjj entry l (l < 21) / vj[l - 21] fuses its v-row product (LIN_FUSE_CD); clear: LIN_FUSE_AB ...
+  uint32_t none;  // ... except where this bit is set: LIN_FUSE_NONE
+  int cw;         // the sums of C and w (dk:320-321)
+  int jzu;        // Jzu = fx (t0 d - t2 (x d^2))
+  int xy[2];      // the fp64 point: R0 X0 + R1 X1 of x, R3 X0 + R4 X1 of y (z fuses its first product everywhere)
+  __device__ int of(int l) const { return ((none >> l) & 1) ? LIN_FUSE_NONE : (((cd >> l) & 1) ? LIN_FUSE_CD : LIN_FUSE_AB); }
+};
+template <bool DEPTH, bool EROWS>
+__device__ __forceinline__ constexpr LinFuse lin_fuse(int p) {
+  if (EROWS) return LinFuse{0x1442a80u, 0x4000000u, LIN_FUSE_NONE, LIN_FUSE_AB, {LIN_FUSE_AB, LIN_FUSE_CD}};   // both pixels alike
+  if (p == 0) return LinFuse{0x1441544u, 0x4000000u, LIN_FUSE_AB, LIN_FUSE_CD, {LIN_FUSE_AB, DEPTH ? LIN_FUSE_AB : LIN_FUSE_CD}};
+  return LinFuse{0x1051544u, 0x4000000u, LIN_FUSE_AB, LIN_FUSE_AB, {LIN_FUSE_CD, LIN_FUSE_AB}};
+}
+__device__ __forceinline__ double lin_dsum2(int how, double a, double b, double c, double d) {   // lin_sum2 in fp64
+#pragma clang fp contract(off)
+  return how == LIN_FUSE_AB ? fma(a, b, c * d) : fma(c, d, a * b);
+}
+// se3.hpp: linearize_pixel_d + pix_jacobians
+__device__ __forceinline__ PixLin lin_pixel_pinned(const Intr& K, const double* R, const double* t, double X0, double X1,
+                                                   float disp, float tu, float tv, const LinFuse f) {
+#pragma clang fp contract(off)
+  const int jzu = f.jzu;
+  const double dd = (double)disp;
+  const double xd = fma(dd, t[0], lin_dsum2(f.xy[0], R[0], X0, R[1], X1) + R[2]);
+  const double yd = fma(dd, t[1], lin_dsum2(f.xy[1], R[3], X0, R[4], X1) + R[5]);
+  const double zd = fma(dd, t[2], lin_dsum2(LIN_FUSE_AB, R[6], X0, R[7], X1) + R[8]);
+  const bool bad = zd < (double)DROID_MIN_DEPTH;
+  double rd = (double)(1.0f / (float)zd);
+  rd = rd * fma(-zd, rd, 2.0);
+  rd = rd * fma(-zd, rd, 2.0);
+  if (bad) rd = 0.0;
+  PixLin L;
+  L.valid = bad ? 0.f : 1.f;
+  L.ru = (float)((double)tu - fma((double)K.fx * rd, xd, (double)K.cx));
+  L.rv = (float)((double)tv - fma((double)K.fy * rd, yd, (double)K.cy));
+  const float x = (float)xd, y = (float)yd, d = (float)rd, h = disp;
+  const float t0 = (float)t[0], t1 = (float)t[1], t2 = (float)t[2];
+  const float d2 = d * d;
+  L.Ju[0] = K.fx * (h * d);
+  L.Ju[1] = 0.f;
+  L.Ju[2] = K.fx * (-x * h * d2);
+  L.Ju[3] = K.fx * (-x * y * d2);
+  L.Ju[4] = K.fx * fmaf(x * x, d2, 1.f);
+  L.Ju[5] = K.fx * (-y * d);
+  L.Jzu = K.fx * lin_sum2(jzu, t0, d, -t2, x * d2);
+  L.Jv[0] = 0.f;
+  L.Jv[1] = K.fy * (h * d);
+  L.Jv[2] = K.fy * (-y * h * d2);
+  L.Jv[3] = K.fy * fmaf(-(y * y), d2, -1.f);
+  L.Jv[4] = K.fy * (x * y * d2);
+  L.Jv[5] = K.fy * (x * d);
+  L.Jzv = K.fy * lin_sum2(LIN_FUSE_AB, t1, d, -t2, y * d2);
+  return L;
+}
+// C, w, Hjj (21) and vj (6) of one pixel; wu, wv: in the raw weights, out the weights of the pose terms
+template <bool DEPTH>
+__device__ __forceinline__ void lin_accumulate_pinned(const PixLin& L, const LinFuse f, bool stereo, float& wu, float& wv,
+                                                      float (&acc)[32], float& Cacc, float& wacc) {
+#pragma clang fp contract(off)
+  wu = L.valid * (0.001f * wu);        // dk:305-306
+  wv = L.valid * (0.001f * wv);
+  if (DEPTH) {
+    Cacc += lin_sum2(f.cw, wu * L.Jzu, L.Jzu, wv * L.Jzv, L.Jzv);         // dk:320, :353
+    wacc += lin_sum2(f.cw, wu * L.ru, L.Jzu, wv * L.rv, L.Jzv);           // dk:321, :354
+  }
+  if (stereo) {  // dk:323, :356
+    wu = 0.f;
+    wv = 0.f;
+  }
+  int l = 0;
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+    const float wa_u = wu * L.Ju[a], wa_v = wv * L.Jv[a];
+#pragma unroll
+    for (int b = 0; b <= a; b++) {
+      acc[l] += lin_sum2(f.of(l), wa_u, L.Ju[b], wa_v, L.Jv[b]);
+      l++;
+    }
+    acc[21 + a] += lin_sum2(f.of(21 + a), wa_u, L.ru, wa_v, L.rv);
+  }
+}
+// E row of one (edge, pixel), dk:341, :374
+__device__ __forceinline__ void lin_erow_pinned(const PixLin& L, float wu, float wv, float (&eij)[6]) {
+#pragma clang fp contract(off)
+  const float su = wu * L.Jzu, sv = wv * L.Jzv;
+  constexpr int EF[6] = {LIN_FUSE_CD, LIN_FUSE_AB, LIN_FUSE_AB, LIN_FUSE_AB, LIN_FUSE_CD, LIN_FUSE_AB};
+#pragma unroll
+  for (int n = 0; n < 6; n++) eij[n] = lin_sum2(EF[n], su, L.Ju[n], sv, L.Jv[n]);
+}
+// its share of the self row: eii = Adj^T eij (se3.hpp: adjT_mat)
+__device__ __forceinline__ void lin_self_pinned(const double* R, const double* t, const float (&eij)[6], float (&eii)[6]) {
+#pragma clang fp contract(off)
+  const float t0 = (float)t[0], t1 = (float)t[1], t2 = (float)t[2];
+  const float u[3] = {eij[3] + lin_sum2(LIN_FUSE_AB, eij[1], t2, -eij[2], t1),
+                      eij[4] + lin_sum2(LIN_FUSE_AB, eij[2], t0, -eij[0], t2),
+                      eij[5] + lin_sum2(LIN_FUSE_CD, eij[0], t1, -eij[1], t0)};
+  constexpr int YF[6] = {LIN_FUSE_AB, LIN_FUSE_CD, LIN_FUSE_CD, LIN_FUSE_AB, LIN_FUSE_CD, LIN_FUSE_AB};
+#pragma unroll
+  for (int n = 0; n < 3; n++) {
+    const float r0 = (float)R[n], r1 = (float)R[3 + n], r2 = (float)R[6 + n];
+    eii[n] = fmaf(r2, eij[2], lin_sum2(YF[n], r0, eij[0], r1, eij[1]));
+    eii[3 + n] = fmaf(r2, u[2], lin_sum2(YF[3 + n], r0, u[0], r1, u[1]));
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // linearisation.  grid (slots or edges, pixel chunks), 256 threads, LIN_PPT pixels per thread.
 // DEPTH = true : blockIdx.x = depth slot; walks the slot's edges; writes per-(edge,chunk) Hjj/vj
 //                partial sums, Q = 1/C, w and the E rows (projective_transform_kernel :176-424
@@ -442,8 +574,9 @@ __global__ __launch_bounds__(1024) void ba_prep_kernel(BaView vg, const int64_t*
 // EROWS (dense graphs): slots that the SYRK-only Schur kernel will serve also get their UNSCALED E rows
 // written to v.Ebuf (row 6*entry + n; the self row Ei = -sum_e Adj^T Eij is accumulated per pixel).
 // ZSPLIT: gridDim.z workgroups share a (slot, chunk), each taking a range of the slot's edges.
-// FULL (host: HW % LIN_CP == 0): every pixel of every chunk exists, the per-lane `pix < HW` guards are compiled out; same
-// arithmetic, same bits.
+// FULL (host: HW % LIN_CP == 0): every pixel of every chunk exists.  The edge loop runs a body of its own: no pixel test, both
+// pixels in one block, its own copy of the per-pixel arithmetic with the roundings of the guarded body written out (above);
+// outside the loop the per-lane `pix < HW` guards are compiled out.  Same bits: tests/test_gpu_lin_pinned.py.
 // The waves of a workgroup never meet inside the edge loop: each reduces its own 128 pixels and stores its own 32
 // words of Hpart (the assemble step adds the four), so a barrier is left only around the metadata (re)loads.
 template <bool DEPTH, bool EROWS, bool ZSPLIT, bool FULL>
@@ -589,12 +722,42 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
     float acc[32];
 #pragma unroll
     for (int k = 0; k < 32; k++) acc[k] = 0.f;
+    if constexpr (FULL) {
+      // every pixel exists: no test, both pixels of the lane in one basic block (fewer instructions and registers, a
+      // fourth wave per SIMD); the roundings are the ragged body's, pinned in source (lin_pixel_pinned and its neighbours)
+      PixLin L[LIN_PPT];
+      float wu[LIN_PPT], wv[LIN_PPT];
+#pragma unroll
+      for (int p = 0; p < LIN_PPT; p++) {
+        const LinFuse fuse = lin_fuse<DEPTH, EROWS>(p);
+        const float d = DEPTH ? disp[p] : disps[(size_t)ix * HW + pix[p]];
+        L[p] = lin_pixel_pinned(K, Rt, Rt + 9, X0d[p], X1d[p], d, in_cur[p][0], in_cur[p][1], fuse);
+        wu[p] = in_cur[p][2];
+        wv[p] = in_cur[p][3];
+        lin_accumulate_pinned<DEPTH>(L[p], fuse, stereo, wu[p], wv[p], acc, Cacc[p], wacc[p]);
+      }
+      if (DEPTH && EROWS && emit) {
+        const int a = sm.ent[xl];
+#pragma unroll
+        for (int p = 0; p < LIN_PPT; p++) {
+          float eij[6];
+          lin_erow_pinned(L[p], wu[p], wv[p], eij);
+          if (a >= 0) {
+#pragma unroll
+            for (int n = 0; n < 6; n++) v.Ebuf[ebuf_index(e0, erows, HW, 6 * a + n, pix[p])] = eij[n];
+          }
+          if (has_self) {
+            float eii[6];
+            lin_self_pinned(Rt, Rt + 9, eij, eii);
+#pragma unroll
+            for (int n = 0; n < 6; n++) selfacc[p][n] -= eii[n];
+          }
+        }
+      }
+    } else {
 #pragma unroll
     for (int p = 0; p < LIN_PPT; p++) {
-      // FULL: a wave-uniform test per pixel row of the chunk (always true there) instead of the per-lane guard.  It is
-      // not dropped altogether: with both pixels in one basic block the SLP vectoriser pairs them and the backend
-      // contracts other multiply-adds, which changes the rounding of Hpart, Q and w (profiles/lin_reduce_ab.txt)
-      if (FULL ? (chunk * LIN_CP + p * LIN_THREADS < HW) : (pix[p] < HW)) {
+      if (pix[p] < HW) {
         const int k = pix[p];
         const float d = DEPTH ? disp[p] : disps[(size_t)ix * HW + k];
         const PixLin L = linearize_pixel_d(K, Rt, Rt + 9, X0d[p], X1d[p], d, in_cur[p][0], in_cur[p][1]);
@@ -639,6 +802,7 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
         }
       }
     }
+    }  // ragged body
     // wave sum of the 27 block entries -> Hpart[e][chunk][wave][0..31] (words 27..31: zeros; all 32 are written)
     const float tot = wave_reduce32(acc);
     if ((lane & 1) == 0) v.Hpart[(((size_t)e * v.nch + chunk) * LIN_WAVES + wave) * 32 + reduce32_index(lane)] = tot;
@@ -2117,28 +2281,44 @@ static auto lin_kernel_of(bool wide, bool zsplit, bool full) {
   return full ? lin_kernel_of<true>(wide, zsplit) : lin_kernel_of<false>(wide, zsplit);
 }
 
+// stage 0 of the build phase.  full: the FULL body of ba_lin_kernel (needs HW % LIN_CP == 0)
+static void launch_lin_stage(const BaView& v, const BaLaunchPlan& plan, const float* poses, const float* disps,
+                             const float* intr, const float* sens, const float* targets, const float* weights,
+                             const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only, bool full,
+                             hipStream_t s) {
+  const bool depth = !motion_only && v.M > 0;
+  if (depth) {
+    const dim3 g(v.M + plan.zero_wgs, v.nch, v.zsplit), b(LIN_THREADS);
+    const auto lin = lin_kernel_of(v.wide != 0, v.zsplit > 1, full);
+    hipLaunchKernelGGL(lin, g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
+    if (v.zsplit > 1)
+      hipLaunchKernelGGL(ba_lin_finish_kernel, dim3(v.M, (v.HW + 255) / 256), dim3(256), 0, s, v, disps, sens, eta);
+  } else if (v.E > 0) {
+    const auto lin = full ? ba_lin_kernel<false, false, false, true> : ba_lin_kernel<false, false, false, false>;
+    hipLaunchKernelGGL(lin, dim3(v.E + plan.zero_wgs, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
+                       disps, intr, sens, targets, weights, eta, ii, jj, v.E);
+  } else {
+    if (v.packed) (void)hipMemsetAsync(v.psys, 0, sizeof(double) * pk_total(v.n), s);
+    else (void)hipMemsetAsync(v.sys, 0, sizeof(double) * (size_t)(v.n + 1) * v.ld, s);
+  }
+}
+
+// test hook (droid_test_ba_lin): the linearisation alone, on request with the ragged body where the FULL one would run
+void launch_lin_test(const BaView& v, const float* poses, const float* disps, const float* intr, const float* sens,
+                     const float* targets, const float* weights, const float* eta, const int64_t* ii, const int64_t* jj,
+                     bool motion_only, bool ragged, hipStream_t s) {
+  launch_lin_stage(v, ba_launch_plan(v), poses, disps, intr, sens, targets, weights, eta, ii, jj, motion_only,
+                   !ragged && v.HW % LIN_CP == 0, s);
+}
+
 void launch_build_stage(const BaView& v, const BaLaunchPlan& plan, const float* poses, const float* disps,
                         const float* intr, const float* sens, const float* targets, const float* weights,
                         const float* eta, const int64_t* ii, const int64_t* jj, bool motion_only,
                         int stage, hipStream_t s) {
   const bool depth = !motion_only && v.M > 0;
-  const bool full = v.HW % LIN_CP == 0;  // no ragged chunk: the linearisation without per-lane pixel guards
   switch (stage) {
-    case 0:
-      if (depth) {
-        const dim3 g(v.M + plan.zero_wgs, v.nch, v.zsplit), b(LIN_THREADS);
-        const auto lin = lin_kernel_of(v.wide != 0, v.zsplit > 1, full);
-        hipLaunchKernelGGL(lin, g, b, 0, s, v, poses, disps, intr, sens, targets, weights, eta, ii, jj, v.M);
-        if (v.zsplit > 1)
-          hipLaunchKernelGGL(ba_lin_finish_kernel, dim3(v.M, (v.HW + 255) / 256), dim3(256), 0, s, v, disps, sens, eta);
-      } else if (v.E > 0) {
-        const auto lin = full ? ba_lin_kernel<false, false, false, true> : ba_lin_kernel<false, false, false, false>;
-        hipLaunchKernelGGL(lin, dim3(v.E + plan.zero_wgs, v.nch), dim3(LIN_THREADS), 0, s, v, poses,
-                           disps, intr, sens, targets, weights, eta, ii, jj, v.E);
-      } else {
-        if (v.packed) (void)hipMemsetAsync(v.psys, 0, sizeof(double) * pk_total(v.n), s);
-        else (void)hipMemsetAsync(v.sys, 0, sizeof(double) * (size_t)(v.n + 1) * v.ld, s);
-      }
+    case 0:  // (no ragged chunk: the linearisation without per-lane pixel guards)
+      launch_lin_stage(v, plan, poses, disps, intr, sens, targets, weights, eta, ii, jj, motion_only, v.HW % LIN_CP == 0, s);
       break;
     case 1:  // (with depth slots the assemble step rides in spare workgroups of the Schur launch, stage 2)
       if (v.E > 0 && !depth)

@@ -75,14 +75,23 @@ ABI_UPDATE = {
     "droid_ba_inputs": ("i", "11p 9i f 6p i 3p i 2p z p"),
 }
 SYMBOLS_UPDATE = list(ABI_UPDATE)
+# The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
+# A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
+# prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
+# and requires none: a build from before a hook existed still loads through DROID_HIP_LIB (tools/ab_test.sh,
+# tools/update_bits.py).
+ABI_TEST = {
+    "droid_test_ba_lin": ("i", "9p 9i p z 4p Z p"),
+}
+SYMBOLS_TEST = list(ABI_TEST)
 _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
           "p": ctypes.c_void_p, "P": ctypes.POINTER(ctypes.c_void_p), "I": ctypes.POINTER(ctypes.c_int),
           "Z": ctypes.POINTER(ctypes.c_size_t), "s": ctypes.c_char_p}
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI or ABI_UPDATE as ctypes types."""
-    res, args = ABI[name] if name in ABI else ABI_UPDATE[name]
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE or ABI_TEST as ctypes types."""
+    res, args = ABI[name] if name in ABI else (ABI_TEST[name] if name in ABI_TEST else ABI_UPDATE[name])
     return _CTYPE[res], [_CTYPE[run[-1]] for run in args.split() for _ in range(int(run[:-1] or 1))]
 
 
@@ -106,8 +115,10 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS + SYMBOLS_UPDATE:
+    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_TEST:
         if not hasattr(lib, s):
+            if s in SYMBOLS_TEST:
+                continue
             raise DroidBackendError(f"{LIB_PATH} does not export {s}")
         fn = getattr(lib, s)
         fn.restype, fn.argtypes = signature(s)
