@@ -446,6 +446,8 @@ __global__ __launch_bounds__(1024) void ba_prep_kernel(BaView vg, const int64_t*
 // every separate multiply and add a plain operator; where an operation is packed, each half rounds like its scalar form.  The
 // pattern was read from the ragged instantiations' instruction selection (hipcc -O3 --offload-arch=gfx950); the test
 // tests/test_gpu_lin_pinned.py holds FULL against the ragged body bit for bit (droid_test_ba_lin forces the latter).
+// That test sees the fp32 fusions on any input; the fp64 ones (lin_dsum2, the Newton steps, ru / rv) show only on the directed
+// inputs of tests/test_gpu_lin_directed.py, where the float that is read is the small difference of two large fp64 terms.
 // Nothing here is shared with another kernel: the helpers of se3.hpp and their contraction stay as they are.
 // ------------------------------------------------------------------------------------------
 // a*b + c*d, rounded as ...
@@ -562,6 +564,39 @@ __device__ __forceinline__ void lin_self_pinned(const double* R, const double* t
     eii[n] = fmaf(r2, eij[2], lin_sum2(YF[n], r0, eij[0], r1, eij[1]));
     eii[3 + n] = fmaf(r2, u[2], lin_sum2(YF[3 + n], r0, u[0], r1, u[1]));
   }
+}
+
+// The relative pose of a motion-only edge (se3.hpp: rel_pose_mat<double>), which every lane of that instantiation
+// evaluates for itself.  Inlined into the FULL and into the ragged body, rel_pose_mat was contracted differently (the sum
+// and the difference of a pair of products, as in R[1] and R[3], shared one rounded product in one body and rounded one
+// product each in the other), so R and t of the two bodies differed by an fp64 ulp on some edges -- and with them ru / rv
+// where the residual is at rounding level (tests/test_gpu_lin_directed.py, zero_residual).  There is no fusion to copy
+// here that would hold from one compilation to the next, so both bodies round every product and every sum on its own.
+__device__ __forceinline__ void lin_rel_pose_pinned(const float* __restrict__ poses, int ix, int jx, double (&Rt)[12]) {
+#pragma clang fp contract(off)
+  if (ix == jx) {  // stereo pair: fixed baseline, the reference's fp32 literal (dk:221)
+#pragma unroll
+    for (int n = 0; n < 9; n++) Rt[n] = (n % 4) == 0 ? 1.0 : 0.0;
+    Rt[9] = (double)(-0.1f);
+    Rt[10] = 0.0;
+    Rt[11] = 0.0;
+    return;
+  }
+  const float* pi = poses + 7 * (size_t)ix;
+  const float* pj = poses + 7 * (size_t)jx;
+  const double ti[3] = {pi[0], pi[1], pi[2]};
+  const double qi[4] = {pi[3], pi[4], pi[5], pi[6]};
+  const double tj[3] = {pj[0], pj[1], pj[2]};
+  const double qj[4] = {pj[3], pj[4], pj[5], pj[6]};
+  const double x = -qj[3] * qi[0] + qj[0] * qi[3] - qj[1] * qi[2] + qj[2] * qi[1];
+  const double y = -qj[3] * qi[1] + qj[1] * qi[3] - qj[2] * qi[0] + qj[0] * qi[2];
+  const double z = -qj[3] * qi[2] + qj[2] * qi[3] - qj[0] * qi[1] + qj[1] * qi[0];
+  const double w = qj[3] * qi[3] + qj[0] * qi[0] + qj[1] * qi[1] + qj[2] * qi[2];
+  Rt[0] = 1.0 - 2.0 * (y * y + z * z); Rt[1] = 2.0 * (x * y - z * w);       Rt[2] = 2.0 * (x * z + y * w);
+  Rt[3] = 2.0 * (x * y + z * w);       Rt[4] = 1.0 - 2.0 * (x * x + z * z); Rt[5] = 2.0 * (y * z - x * w);
+  Rt[6] = 2.0 * (x * z - y * w);       Rt[7] = 2.0 * (y * z + x * w);       Rt[8] = 1.0 - 2.0 * (x * x + y * y);
+#pragma unroll
+  for (int n = 0; n < 3; n++) Rt[9 + n] = tj[n] - (Rt[3 * n] * ti[0] + Rt[3 * n + 1] * ti[1] + Rt[3 * n + 2] * ti[2]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -699,11 +734,7 @@ __global__ __launch_bounds__(LIN_THREADS, 3) void ba_lin_kernel(
       stereo = sm.flag[xl] != 0;
     } else {
       const int jx = (int)jj[e];
-      const RelMat<double> T = rel_pose_mat<double, true>(poses, ix, jx);
-#pragma unroll
-      for (int n = 0; n < 9; n++) Rt[n] = T.R[n];
-#pragma unroll
-      for (int n = 0; n < 3; n++) Rt[9 + n] = T.t[n];
+      lin_rel_pose_pinned(poses, ix, jx, Rt);   // the same roundings in the FULL and in the ragged body
       stereo = (ix == jx);
     }
     // software pipeline: the next edge's targets / weights are in flight while this one is reduced

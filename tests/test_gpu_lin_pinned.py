@@ -21,10 +21,9 @@ import pytest
 
 import hard_scenes as hs
 import stage_graphs as sg
-from util import to_dev
+from lin_hook import LIN_CP, instantiation, run_lin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIN_CP, LIN_WAVES, LIN_WGS = 512, 4, 1536     # csrc/ba_internal.hpp
 
 
 def _band(N, reach):
@@ -70,18 +69,6 @@ CASES = {
     "hard_dense36_syrk": (lambda s: hs.SCENES["hard_dense36_syrk"].problem(), False, (1, 1, 1)),
     "hard_motion_only": (lambda s: hs.SCENES["hard_motion_only"].problem(), True, (0, 0, 0)),
 }
-
-
-def instantiation(p, motion_only):
-    """(depth, E rows, edge ranges) of the ba_lin_kernel the host launches (ba_internal.hpp::ba_carve, launch_build_stage),
-    restated so that the table can be checked without a GPU; run_lin holds it against what the library reports."""
-    _, H, W = p.disps.shape
-    if motion_only:
-        return (0, 0, 0)
-    M, E, nch = p.eta.shape[0], len(p.ii), (H * W + LIN_CP - 1) // LIN_CP
-    wide = M > 0 and E >= 12 * M and (H * W) % 32 == 0
-    zsplit = min(max(LIN_WGS // (M * nch), 1), 8)
-    return (1, int(wide), int(zsplit > 1))
 
 
 @pytest.fixture(scope="module")
@@ -132,41 +119,6 @@ def test_hook_table_matches_its_header(backends):
         assert fn.restype == restype and list(fn.argtypes) == argtypes, name
     rc = lib.droid_test_ba_lin(*([None] * 9), 4, 8, 16, 32, 8, 5, 3, 0, 0, None, 0, None, None, None, None, None, None)
     assert rc == -1 and b"window" in lib.droid_last_error()          # refused on the host, no GPU needed
-
-
-def run_lin(backends, p, motion_only, ragged):
-    """The linearisation of `p` on a zeroed workspace of its own after droid_ba_prepare, with the FULL (ragged = 0) or
-    the ragged body; returns {name: int32 numpy view} of what the hook copies out."""
-    import torch
-    from droid_backends._args import _stream
-    from droid_backends.ba_binding import BAProblemDev, BaBinding
-    lib = backends._lib.load()
-    d = BAProblemDev(**to_dev(p, torch))
-    b = BaBinding(status_mirror=False, headroom=(1, 0))
-    try:
-        E, nbuf, H, W, M, t0, t1 = b.begin(d, p.t0, p.t1, motion_only)
-        b.buf.zero_()
-        b.prepare(d, (0, nbuf), motion_only)
-        ws = (b.buf.data_ptr(), b.buf.numel())
-        args = (*b._build_args(d), int(motion_only), int(ragged), *ws)
-        words = (ctypes.c_size_t * 6)()
-        backends._lib.check(lib.droid_test_ba_lin(*args, None, None, None, None, words, _stream()), "test_ba_lin (sizes)")
-        nch = (H * W + LIN_CP - 1) // LIN_CP
-        # the instantiation the HOST chooses (words 4, 5: E rows kept, edge ranges) is the one the table names
-        assert (int(not motion_only), 0 if motion_only else int(words[4]), 0 if motion_only else int(words[5] > 1)) == \
-            instantiation(p, motion_only), (int(words[4]), int(words[5]))
-        words = list(words)[:4]
-        assert words[0] == E * nch * LIN_WAVES * 32 and words[1] == words[2] == M * H * W
-        assert words[3] in (0, 6 * (M + E) * H * W)
-        out = [torch.full((max(int(n), 1),), float("nan"), dtype=torch.float32, device="cuda") for n in words]
-        ptr = [o.data_ptr() if n else None for o, n in zip(out, words)]
-        backends._lib.check(lib.droid_test_ba_lin(*args, *ptr, None, _stream()), "test_ba_lin")
-        torch.cuda.synchronize()
-        st, _ = b.status()
-        assert st & 15 == 0, st
-    finally:
-        b.close()
-    return {k: o[:int(n)].view(torch.int32).cpu().numpy() for k, o, n in zip(("Hpart", "Q", "w", "Ebuf"), out, words)}
 
 
 @pytest.mark.gpu
