@@ -928,4 +928,31 @@ int droid_ba_inputs(const int64_t* ii, const int64_t* jj, const float* a, const 
   return check_hip("ba_inputs");
 }
 
+// ---------------------------------------------------------------------------- corr_encode (droid_update_hip.h)
+size_t droid_corr_encode_packed_bytes(void) { return DROID_CORR_ENCODE_PACKED_BYTES; }
+
+int droid_corr_encode(const void* const* volumes, const int64_t* slots, const float* coords, const void* packed, void* out,
+                      int B, int64_t cap, int H1, int W1, int radius, int levels, int out_channels, int dtype,
+                      int coords_layout, void* stream) {
+  if (B < 0 || B > 65535) return fail(DROID_E_ARG, "corr_encode: bad %s", "B (0 .. 65535)");
+  if (H1 < 1 || W1 < 1 || (long long)H1 * W1 > (1ll << 30))
+    return fail(DROID_E_ARG, "corr_encode: bad %s", "map size (H1, W1 >= 1, H1 * W1 <= 2^30)");
+  if (radius != 3) return fail(DROID_E_ARG, "corr_encode: bad %s", "radius (3)");
+  if (levels != 4) return fail(DROID_E_ARG, "corr_encode: bad %s", "levels (4)");
+  if (out_channels != 128) return fail(DROID_E_ARG, "corr_encode: bad %s", "out_channels (128)");
+  if (cap < 1 || (!slots && cap < B)) return fail(DROID_E_ARG, "corr_encode: bad %s", "cap (at least 1; at least B without slots)");
+  if (coords_layout != DROID_COORDS_2HW && coords_layout != DROID_COORDS_HW2)
+    return fail(DROID_E_ARG, "corr_encode: bad %s", "coords_layout (DROID_COORDS_2HW or DROID_COORDS_HW2)");
+  if (dtype != DROID_F16 && dtype != DROID_F32) return fail(DROID_E_ARG, "corr_encode: bad %s", "dtype (f16 or f32)");
+  if (B == 0) return DROID_OK;
+  if (!volumes || !coords || !packed || !out) return fail(DROID_E_ARG, "corr_encode: null %s", "pointer");
+  for (int l = 0; l < levels; l++)   // a level without pixels (H1 or W1 below 2^l) is never read and may be NULL
+    if (!volumes[l] && (H1 >> l) > 0 && (W1 >> l) > 0) return fail(DROID_E_ARG, "corr_encode: null %s", "pyramid level");
+  if (((uintptr_t)packed & 15) != 0) return fail(DROID_E_ARG, "corr_encode: %s", "packed is not 16-byte aligned");
+  int rc = launch_corr_encode(volumes, slots, (long long)(slots ? cap : (int64_t)B), coords, packed, out, B, H1, W1, dtype,
+                              coords_layout == DROID_COORDS_HW2, (hipStream_t)stream);
+  if (rc) return fail(rc, "corr_encode: %s", "unsupported configuration");
+  return check_hip("corr_encode");
+}
+
 }  // extern "C"

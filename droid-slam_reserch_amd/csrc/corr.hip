@@ -115,12 +115,23 @@ static void with_radius(int r, F&& f) {
 // ---- the bilinear combine of one query: (2r+1)^2 outputs from (2r+2)^2 taps ---------------------------------
 // out(a, c) = ((tap[c][a] w00 + tap[c+1][a] w01) + tap[c][a+1] w10) + tap[c+1][a+1] w11, every product and every sum rounded
 // to the element type (ck:55-66); output plane a (2r+1) + c.
+// Where the outputs go is the destination's business: PlaneDst writes output k to plane k of a lookup's result, TileDst
+// (corr_encode, below) writes it as a half to column k of an LDS row.  put() takes a work value, put_h() a half as the
+// packed combine holds it.
+template <typename T>
+struct PlaneDst {
+  T* __restrict__ out;  // element (b, plane 0, pix)
+  int H1W1;
+  __device__ __forceinline__ void put(int k, typename Elem<T>::work v) const { Elem<T>::store(out + (size_t)k * H1W1, v); }
+  __device__ __forceinline__ void put_h(int k, _Float16 v) const { reinterpret_cast<_Float16*>(out)[(size_t)k * H1W1] = v; }
+};
 template <typename T, int R>
 struct Combine {
   typedef typename Elem<T>::work work;
   static constexpr int RD = 2 * R + 1, NT = RD + 1;
+  template <typename Dst>
   static __device__ __forceinline__ void run(const work (&tap)[NT][NT], work w00, work w01, work w10, work w11,
-                                             T* __restrict__ out, int H1W1) {
+                                             const Dst& dst) {
 #pragma unroll
     for (int a = 0; a < RD; a++) {
 #pragma unroll
@@ -129,7 +140,7 @@ struct Combine {
         acc = Elem<T>::add(acc, Elem<T>::mul(tap[c + 1][a], w01));
         acc = Elem<T>::add(acc, Elem<T>::mul(tap[c][a + 1], w10));
         acc = Elem<T>::add(acc, Elem<T>::mul(tap[c + 1][a + 1], w11));
-        Elem<T>::store(out + (size_t)(a * RD + c) * H1W1, acc);
+        dst.put(a * RD + c, acc);
       }
     }
   }
@@ -147,8 +158,9 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 template <int R>
 struct Combine<__half, R> {
   static constexpr int RD = 2 * R + 1, NT = RD + 1;
+  template <typename Dst>
   static __device__ __forceinline__ void run(const float (&tap)[NT][NT], float w00, float w01, float w10, float w11,
-                                             __half* __restrict__ out, int H1W1) {
+                                             const Dst& dst) {
     // P[j][i] = (tap[j][i], tap[j][i+1]); the taps are halves held in floats: the pack is exact
     f16x2 P[NT][NT];
 #pragma unroll
@@ -160,7 +172,6 @@ struct Combine<__half, R> {
     const f16x2 W01 = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(w01, w01));
     const f16x2 W10 = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(w10, w10));
     const f16x2 W11 = __builtin_bit_cast(f16x2, __builtin_amdgcn_cvt_pkrtz(w11, w11));
-    _Float16* o = reinterpret_cast<_Float16*>(out);
 #pragma unroll
     for (int a = 0; a < RD; a += 2) {
 #pragma unroll
@@ -169,8 +180,8 @@ struct Combine<__half, R> {
         acc = acc + P[c + 1][a] * W01;
         acc = acc + P[c][a + 1] * W10;
         acc = acc + P[c + 1][a + 1] * W11;
-        o[(size_t)(a * RD + c) * H1W1] = acc[0];
-        if (a + 1 < RD) o[(size_t)((a + 1) * RD + c) * H1W1] = acc[1];
+        dst.put_h(a * RD + c, acc[0]);
+        if (a + 1 < RD) dst.put_h((a + 1) * RD + c, acc[1]);
       }
     }
   }
@@ -274,8 +285,11 @@ struct Lookup {
   // valid = false: a lane without a query (pix is then any pixel that exists)
   __device__ __forceinline__ void locate(const float* __restrict__ coords, int b, int pix, int H1W1, int W2, float cscale,
                                          bool valid = true) {
-    const float x0 = coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale;
-    const float y0 = coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale;
+    locate_xy(coords[((size_t)b * 2 + 0) * H1W1 + pix] * cscale, coords[((size_t)b * 2 + 1) * H1W1 + pix] * cscale, W2,
+              valid);
+  }
+  // the same from the scaled coordinate pair itself (corr_encode reads a pixel's pair once for all levels)
+  __device__ __forceinline__ void locate_xy(float x0, float y0, int W2, bool valid = true) {
     bl = bilin_setup(x0, y0, R);
     xany = valid && live && (bl.x1 + NT > 0) && (bl.x1 < W2);
   }
@@ -287,9 +301,54 @@ struct Lookup {
     work w00 = w.w00, w01 = w.w01, w10 = w.w10, w11 = w.w11;
     if (!live) w00 = w01 = w10 = w11 = (work)0;
     T* out = corr + (size_t)b * out_bstride + pix;
-    Combine<T, R>::run(tap, w00, w01, w10, w11, out, H1W1);
+    Combine<T, R>::run(tap, w00, w01, w10, w11, PlaneDst<T>{out, H1W1});
+  }
+  // the same (2r+1)^2 values into another destination
+  template <typename Dst>
+  __device__ __forceinline__ void combine_to(const work (&tap)[NT][NT], const Dst& dst) const {
+    const Weights<T> w = bilin_weights<T>(bl);
+    work w00 = w.w00, w01 = w.w01, w10 = w.w10, w11 = w.w11;
+    if (!live) w00 = w01 = w10 = w11 = (work)0;
+    Combine<T, R>::run(tap, w00, w01, w10, w11, dst);
   }
 };
+
+// The window of one lane's query by per-lane row loads, for corr_encode: the gather of corr_index_forward_kernel below,
+// statement for statement.  That kernel keeps its own copy: taking it from here costs it 8 VGPRs (72 -> 80 for half at
+// radius 3) and one of its 7 waves per SIMD.
+template <typename T, int R, bool SLOTTED>
+__device__ __forceinline__ void gather_rows(const Lookup<T, R, SLOTTED>& q, const T* plane, uintptr_t vbeg, uintptr_t vend,
+                                            int H2, int W2, typename Elem<T>::work (&tap)[2 * R + 2][2 * R + 2]) {
+  typedef typename Elem<T>::work work;
+  constexpr int NT = 2 * R + 2;
+#pragma unroll
+  for (int j = 0; j < NT; j++) {
+    const int y1 = q.bl.y1 + j;
+    const bool rowok = q.xany && (y1 >= 0) && (y1 < H2);
+#pragma unroll
+    for (int i = 0; i < NT; i++) tap[j][i] = (work)0;
+    if (rowok) {
+      const T* rp = plane + (ptrdiff_t)y1 * W2 + q.bl.x1;
+      if (row_load_ok<T, NT>(rp, vbeg, vend)) {
+        RowLoad<T, NT>::load(rp, tap[j]);
+      } else {  // first / last elements of the whole tensor only
+#pragma unroll 1
+        for (int i = 0; i < NT; i++) {
+          const int x1 = q.bl.x1 + i;
+          const work v = (x1 >= 0 && x1 < W2) ? Elem<T>::load(rp + i) : (work)0;
+#pragma unroll
+          for (int i2 = 0; i2 < NT; i2++)
+            if (i2 == i) tap[j][i2] = v;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < NT; i++) {
+        const int x1 = q.bl.x1 + i;
+        if (x1 < 0 || x1 >= W2) tap[j][i] = (work)0;
+      }
+    }
+  }
+}
 
 template <typename T, int R, bool SLOTTED>
 __global__ __launch_bounds__(256, CORR_MINWG) void corr_index_forward_kernel(const T* __restrict__ volume,
@@ -651,6 +710,168 @@ int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t*
     case DROID_F64: return corr_pyramid_forward_t<double, true>(volumes, slots, cap, coords, corr, B, H1, W1, r, levels, s);
   }
   return DROID_E_ARG;
+}
+
+// ---- corr_encode: the 4-level radius-3 lookup fused with corr_encoder[0:2] (include/droid_update_hip.h) -------------
+// One wave per workgroup owns 64 consecutive pixels of one batch entry.  Per level: every lane gathers the window of its
+// pixel (gather_rows: the loads of corr_index_forward_kernel) and Combine writes the 49 halves into the lane's row of an
+// LDS A tile [64 pixels][64 K] (row pitch 72 halves: 16-byte aligned rows); columns 49..63 are zeroed by the kernel once
+// and never written again.  The tile then meets the level's packed weights in 2 x 4 x 8 v_mfma_f32_16x16x32_f16 (K steps
+// x pixel tiles x channel tiles); the 4 x 8 accumulator fragments (128 registers) live across the four levels.  MFMA tile
+// t takes as its row r the pixel 16 (r >> 2) + 4 t + (r & 3), so that a lane's 16 accumulator elements of one channel are
+// 16 CONSECUTIVE pixels: the epilogue (bias, one rounding to half, max with 0) stores them with two 16-byte stores, and
+// the four lanes of a channel cover the wave's 64 pixels as one contiguous 128-byte segment.
+constexpr int CE_LEVELS = 4, CE_R = 3, CE_K = 49, CE_KP = 64, CE_N = 128, CE_PITCH = 72;
+static_assert(CE_K == (2 * CE_R + 1) * (2 * CE_R + 1) && CE_K <= CE_KP && CE_KP + 8 == CE_PITCH, "A tile: 49 of 64 columns");
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct TileDst {
+  _Float16* row;  // the lane's row of the A tile
+  __device__ __forceinline__ void put(int k, float v) const {  // fp32 pyramids: the autocast cast, nearest-even, overflow to inf
+    const __half h = __float2half_rn(v);
+    row[k] = __builtin_bit_cast(_Float16, h);
+  }
+  __device__ __forceinline__ void put_h(int k, _Float16 v) const { row[k] = v; }
+};
+
+template <typename T>
+struct EncodeLevels {
+  const T* v[CE_LEVELS];
+};
+
+// epilogue of one channel tile: lane (g, c16) holds, for channel n, the pixels p0 + 4 t + i in acc[t][i]
+__device__ __forceinline__ void ce_store(const f32x4 (&acc)[4], int n, const __half* __restrict__ b16, __half* __restrict__ y,
+                                         int b, int H1W1, int p0, bool wide) {
+  const float bias = __half2float(b16[n]);
+  __half* o = y + ((size_t)b * CE_N + n) * H1W1 + p0;
+  unsigned short h[16];
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const __half r = __float2half_rn(acc[t][i] + bias);
+      const float rf = __half2float(r);
+      // max(., 0) that keeps a NaN: +0 for everything that is not above zero
+      h[4 * t + i] = (rf > 0.f || rf != rf) ? __half_as_ushort(r) : (unsigned short)0;
+    }
+  if (wide) {
+    uint4 v0, v1;
+    v0.x = h[0] | ((uint32_t)h[1] << 16); v0.y = h[2] | ((uint32_t)h[3] << 16);
+    v0.z = h[4] | ((uint32_t)h[5] << 16); v0.w = h[6] | ((uint32_t)h[7] << 16);
+    v1.x = h[8] | ((uint32_t)h[9] << 16); v1.y = h[10] | ((uint32_t)h[11] << 16);
+    v1.z = h[12] | ((uint32_t)h[13] << 16); v1.w = h[14] | ((uint32_t)h[15] << 16);
+    reinterpret_cast<uint4*>(o)[0] = v0;
+    reinterpret_cast<uint4*>(o)[1] = v1;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+      if (p0 + k < H1W1) o[k] = __ushort_as_half(h[k]);
+  }
+}
+
+// Two waves per SIMD (219 / 238 VGPRs for half / fp32 pyramids, accumulators included): without the attribute the
+// compiler spreads over 146 + 128 registers and one wave per SIMD is left to hide the gather's latency
+// (profiles/corr_encode_ab.txt: 48x64, E = 64: 145.5 us at two waves, 186.0 us at one).
+template <typename T, bool SLOTTED, bool HW2>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void corr_encode_kernel(
+    EncodeLevels<T> vols, const float* __restrict__ coords, const f16x8* __restrict__ wpk, const __half* __restrict__ b16,
+    __half* __restrict__ y, int H1, int W1, const int64_t* __restrict__ slots, long long cap, long long nslots) {
+  typedef Lookup<T, CE_R, SLOTTED> Q;
+  typedef typename Q::work work;
+  constexpr int NT = Q::NT;
+  __shared__ __attribute__((aligned(16))) _Float16 tile[64 * CE_PITCH];
+  const int lane = threadIdx.x, H1W1 = H1 * W1;
+  const int pix0 = blockIdx.x * 64, b = blockIdx.y;
+  const bool valid = pix0 + lane < H1W1;
+  const int pix = valid ? pix0 + lane : H1W1 - 1;  // a lane without a pixel gathers nothing and fills its row with zeros
+  Q q(slots, cap, b);
+  float cx, cy;
+  if constexpr (HW2) {
+    cx = coords[((size_t)b * H1W1 + pix) * 2 + 0];
+    cy = coords[((size_t)b * H1W1 + pix) * 2 + 1];
+  } else {
+    cx = coords[((size_t)b * 2 + 0) * H1W1 + pix];
+    cy = coords[((size_t)b * 2 + 1) * H1W1 + pix];
+  }
+  _Float16* row = tile + lane * CE_PITCH;
+  {  // the padding columns: zeros of the kernel's own, whatever the LDS held (column 48 is rewritten by every level)
+    const uint4 z = {0u, 0u, 0u, 0u};
+    *reinterpret_cast<uint4*>(row + 48) = z;
+    *reinterpret_cast<uint4*>(row + 56) = z;
+  }
+  const int g = lane >> 4, c16 = lane & 15;
+  const int arow = 16 * (c16 >> 2) + (c16 & 3);  // + 4 t: the pixel that is row c16 of MFMA tile t
+  f32x4 acc[8][4];  // [channel tile][pixel tile]
+#pragma unroll
+  for (int nt = 0; nt < 8; nt++)
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[nt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+  for (int l = 0; l < CE_LEVELS; l++) {
+    const int H2 = H1 >> l, W2 = W1 >> l;
+    const float cs = 1.0f / (float)(1 << l);
+    const T* volume = vols.v[l];
+    const size_t plane_elems = (size_t)H2 * W2;
+    const uintptr_t vbeg = reinterpret_cast<uintptr_t>(volume);
+    const uintptr_t vend = vbeg + (size_t)nslots * H1W1 * plane_elems * sizeof(T);
+    q.locate_xy(cx * cs, cy * cs, W2, valid);
+    work tap[NT][NT];
+    gather_rows<T, CE_R, SLOTTED>(q, volume + (q.slot * H1W1 + pix) * plane_elems, vbeg, vend, H2, W2, tap);
+    if (l > 0) __syncthreads();  // the previous level's fragments have been read
+    q.combine_to(tap, TileDst{row});
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+      f16x8 a[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++)
+        a[t] = *reinterpret_cast<const f16x8*>(tile + (arow + 4 * t) * CE_PITCH + s * 32 + g * 8);
+      const f16x8* wl = wpk + ((size_t)(l * 2 + s) * 8) * 64 + lane;
+#pragma unroll
+      for (int nt = 0; nt < 8; nt++) {
+        const f16x8 bf = wl[nt * 64];
+#pragma unroll
+        for (int t = 0; t < 4; t++) acc[nt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], bf, acc[nt][t], 0, 0, 0);
+      }
+    }
+  }
+  const int p0 = pix0 + 16 * g;
+  const bool wide = (H1W1 & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && p0 + 16 <= H1W1;
+#pragma unroll
+  for (int nt = 0; nt < 8; nt++) ce_store(acc[nt], nt * 16 + c16, b16, y, b, H1W1, p0, wide);
+}
+
+template <typename T, bool SLOTTED>
+static void corr_encode_t(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                          const void* packed, void* out, int B, int H1, int W1, int hw2, hipStream_t s) {
+  EncodeLevels<T> vols;
+  for (int l = 0; l < CE_LEVELS; l++) vols.v[l] = static_cast<const T*>(volumes[l]);
+  const f16x8* wpk = static_cast<const f16x8*>(packed);
+  const __half* b16 = static_cast<const __half*>(packed) + (size_t)CE_LEVELS * CE_KP * CE_N;
+  const dim3 grid((H1 * W1 + 63) / 64, B);
+  const long long nslots = SLOTTED ? cap : (long long)B;
+  if (hw2)
+    hipLaunchKernelGGL((corr_encode_kernel<T, SLOTTED, true>), grid, dim3(64), 0, s, vols, coords, wpk, b16,
+                       static_cast<__half*>(out), H1, W1, slots, cap, nslots);
+  else
+    hipLaunchKernelGGL((corr_encode_kernel<T, SLOTTED, false>), grid, dim3(64), 0, s, vols, coords, wpk, b16,
+                       static_cast<__half*>(out), H1, W1, slots, cap, nslots);
+}
+
+// every argument has been checked by droid_corr_encode
+int launch_corr_encode(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                       const void* packed, void* out, int B, int H1, int W1, int dtype, int hw2, hipStream_t s) {
+  if (dtype == DROID_F16) {
+    if (slots) corr_encode_t<__half, true>(volumes, slots, cap, coords, packed, out, B, H1, W1, hw2, s);
+    else corr_encode_t<__half, false>(volumes, slots, cap, coords, packed, out, B, H1, W1, hw2, s);
+  } else if (dtype == DROID_F32) {
+    if (slots) corr_encode_t<float, true>(volumes, slots, cap, coords, packed, out, B, H1, W1, hw2, s);
+    else corr_encode_t<float, false>(volumes, slots, cap, coords, packed, out, B, H1, W1, hw2, s);
+  } else {
+    return DROID_E_ARG;
+  }
+  return 0;
 }
 
 // ---- corr_index_backward (ck:73-124): each query scatters into its own plane -> no races ---

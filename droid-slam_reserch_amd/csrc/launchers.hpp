@@ -14,6 +14,8 @@ int launch_corr_pyramid_forward(const void* const* volumes, const float* coords,
                                 int r, int levels, int dtype, hipStream_t s);
 int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
                                       void* corr, int B, int H1, int W1, int r, int levels, int dtype, hipStream_t s);
+int launch_corr_encode(const void* const* volumes, const int64_t* slots, long long cap, const float* coords,
+                       const void* packed, void* out, int B, int H1, int W1, int dtype, int hw2, hipStream_t s);
 int launch_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
                                int H1, int W1, int H2, int W2, int r, int dtype, hipStream_t s);
 int launch_altcorr_pyramid_forward(const void* const* levels_dev, const int64_t* ii, const int64_t* jj,

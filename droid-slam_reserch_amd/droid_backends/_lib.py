@@ -75,6 +75,13 @@ ABI_UPDATE = {
     "droid_ba_inputs": ("i", "11p 9i f 6p i 3p i 2p z p"),
 }
 SYMBOLS_UPDATE = list(ABI_UPDATE)
+# include/droid_corr_encode_hip.h, the prototypes of the contract stated in droid_update_hip.h (tests/test_corr_encode_abi.py
+# holds the table against them).  A table of its own because tests/test_ba_inputs_abi.py pins ABI_UPDATE at its two entries.
+ABI_CORR_ENCODE = {
+    "droid_corr_encode_packed_bytes": ("z", ""),
+    "droid_corr_encode": ("i", "P 4p i l 7i p"),
+}
+SYMBOLS_CORR_ENCODE = list(ABI_CORR_ENCODE)
 # The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
 # A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
 # prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
@@ -90,8 +97,13 @@ _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": cty
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI, ABI_UPDATE or ABI_TEST as ctypes types."""
-    res, args = ABI[name] if name in ABI else (ABI_TEST[name] if name in ABI_TEST else ABI_UPDATE[name])
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE or ABI_TEST as ctypes types."""
+    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE):
+        if name in table:
+            break
+    else:
+        table = ABI_UPDATE
+    res, args = table[name]
     return _CTYPE[res], [_CTYPE[run[-1]] for run in args.split() for _ in range(int(run[:-1] or 1))]
 
 
@@ -115,7 +127,7 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_TEST:
+    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_TEST:
         if not hasattr(lib, s):
             if s in SYMBOLS_TEST:
                 continue

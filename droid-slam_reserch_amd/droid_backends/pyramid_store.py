@@ -148,3 +148,14 @@ class PyramidStore:
         c = coords.permute(0, 1, 4, 2, 3).contiguous().view(num, 2, ht, wd)
         corr, = corr_pyramid_forward(self.pyramid, c, self.radius, slots=self._slots_dev)
         return corr[None]
+
+    def encode(self, coords1, enc):
+        """coords1 [1, E, h, w, 2] float32 as `reproject` returns it, enc a `CorrEncoder` -> [E, 128, h, w] half:
+        `corr_encoder[0:2]` of `self(coords1)` in one launch, without the lookup tensor and without the permuted copy of
+        the coordinates (droid_corr_encode).  What `corr_encoder[2:]` takes next."""
+        if coords1.dim() != 5 or coords1.shape[0] != 1 or coords1.shape[1] != len(self.table) or coords1.shape[4] != 2:
+            raise RuntimeError(f"PyramidStore.encode: coords1 must be [1, {len(self.table)}, h, w, 2], "
+                               f"got {tuple(coords1.shape)}")
+        if len(self.table) == 0:
+            return torch.empty((0, 128) + tuple(coords1.shape[2:4]), dtype=torch.float16, device=self.fmaps.device)
+        return enc(self.pyramid, coords1[0], slots=self._slots_dev, layout="hw2")

@@ -82,7 +82,53 @@ int droid_ba_inputs(const int64_t *ii, const int64_t *jj, const float *a, const 
                     float *eta, int64_t *frames_active, int64_t *frames_eta, int cap_m, int *info, void *workspace,
                     size_t workspace_bytes, void *stream);
 
+/* The correlation lookup of an update step fused with the first two layers of the update module's correlation encoder:
+ * `CorrBlock.__call__` (droid_slam/modules/corr.py:40-50) followed by `corr_encoder[0:2]`, a Conv2d(196, 128, 1) and a
+ * ReLU under autocast (droid_slam/droid_net.py:83-87, :125), in ONE launch that never writes the [B,196,H1,W1] lookup:
+ *
+ *   y[e, n, p] = relu( half( sum_k a[e,k,p] * w16[n,k]  +  float(b16[n]) ) )          y: [B, 128, H1, W1] half
+ *
+ * a[e,k,p], k = l * 49 + (ix * 7 + iy), is the value droid_corr_pyramid_forward[_slots] yields for channel k of entry e
+ *   at pixel p -- the channel order of torch.cat(out_pyramid).  Half pyramids: those bits.  fp32 pyramids: that fp32
+ *   value rounded to half, nearest-even, overflow to inf (autocast's cast in front of the convolution).  Everything the
+ *   lookup does is inherited, because the kernel calls the lookup's own device functions: border masking, empty windows,
+ *   zeros for non-finite coordinates, the exact 2^-l scaling of the coordinates.
+ * w16 = half(weight), b16 = half(bias), nearest-even from the fp32 parameters (autocast's cast).
+ * Arithmetic: every product a * w16 is exact in fp32; fp32 accumulation (v_mfma_f32_16x16x32_f16), in an order that is
+ *   fixed but not specified; then + float(b16[n]) in fp32, ONE rounding to half, then max(., 0) (+0 for every value not
+ *   above zero; a NaN stays a NaN).  No atomics: the same bits on every run, and the bits of an entry do not depend on
+ *   B, on its position in the batch or on its slot.
+ * slots: NULL, or [B] int64 on the DEVICE as in droid_corr_pyramid_forward_slots: the levels are capacity buffers
+ *   [cap,H1,W1,H1>>l,W1>>l] and entry e reads slot slots[e].  A slot outside [0, cap) gives a = 0 for that entry, so
+ *   its output is relu(b16[n]) everywhere; nothing outside the buffers is read; two entries may name one slot.  With
+ *   slots NULL entry e reads entry e of [cap,...] buffers, cap >= B.
+ * coords: fp32, DROID_COORDS_2HW = [B,2,H1,W1] (x plane, y plane: what the lookup takes) or DROID_COORDS_HW2 =
+ *   [B,H1,W1,2] (`coords1[0]` as reproject / motion_features return it).  The values used are the same either way.
+ * Shapes: radius 3, 4 levels, 128 output channels (the reference's cor_planes), any H1, W1 >= 1 (a level with
+ *   H1 >> l == 0 or W1 >> l == 0 has no taps, contributes zeros, and its pointer is not looked at), B <= 65535.
+ *
+ * packed: the parameters, packed once per network.  DROID_CORR_ENCODE_PACKED_BYTES bytes, 16-byte aligned:
+ *   halves [4 levels][2 K steps][8 channel tiles][64 lanes][8], then b16 [128].  K is padded per level from 49 to 64:
+ *   element (l, s, nt, lane, j) is w16[n][l * 49 + kk] with n = 16 nt + (lane & 15), kk = 32 s + 8 (lane >> 4) + j, and
+ *   ZERO where kk >= 49.  Lane `lane` of a wave thus fetches its B fragment of v_mfma_f32_16x16x32_f16 for (level l,
+ *   K step s, channel tile nt) with one 16-byte load, and a wave's 64 loads are one contiguous KiB.  The kernel writes
+ *   the padding columns 49..63 of its own LDS A tile as zeros itself, whatever the LDS held before.
+ *
+ * Refusals, DROID_E_ARG with a message that names corr_encode and the argument, before any HIP call, sizes before
+ * dtypes before pointers: B outside [0, 65535] ; H1 or W1 < 1 or H1 * W1 > 2^30 ; radius != 3 ; levels != 4 ;
+ * out_channels != 128 ; cap < 1, or cap < B without slots ; a coords_layout that is neither constant ; a dtype other
+ * than F16 / F32 (F64 is refused) ; then, for B > 0: a null volumes / coords / packed / out, a null level that has
+ * pixels, a packed buffer that is not 16-byte aligned.  B == 0 launches nothing and returns DROID_OK.  There is no
+ * fallback: the unfused sequence stays available.
+ * The two prototypes, droid_corr_encode_packed_bytes (host arithmetic: the constant below) and droid_corr_encode, are in
+ * droid_corr_encode_hip.h, included at the end of this header: tests/test_ba_inputs_abi.py pins the prototypes written
+ * in this file, like tests/test_abi.py those of the main header. */
+#define DROID_COORDS_2HW 0
+#define DROID_COORDS_HW2 1
+#define DROID_CORR_ENCODE_PACKED_BYTES (4 * 64 * 128 * 2 + 128 * 2)
+
 #ifdef __cplusplus
 }
 #endif
+#include "droid_corr_encode_hip.h"
 #endif /* DROID_UPDATE_HIP_H */
