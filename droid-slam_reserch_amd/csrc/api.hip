@@ -82,6 +82,14 @@ static int corr_check(const char* name, int B, int N, int H1, int W1, int H2, in
   return DROID_OK;
 }
 
+// The volume lookups and their gradient keep a query pixel index (H1 * W1) and the byte count of one plane (H2 * W2 * 8 for
+// doubles) in 32 bits; element offsets into the volumes are 64-bit.
+static int corr_map_check(const char* name, int H1, int W1, int H2, int W2) {
+  if ((long long)H1 * W1 > (1ll << 27) || (long long)H2 * W2 > (1ll << 27))
+    return fail(DROID_E_ARG, "%s: bad %s", name, "map size (H1 * W1 and H2 * W2 at most 2^27)");
+  return DROID_OK;
+}
+
 extern "C" {
 
 int droid_abi_version(void) { return DROID_ABI_VERSION; }
@@ -91,6 +99,7 @@ const char* droid_last_error(void) { return g_err; }
 int droid_corr_index_forward(const void* volume, const float* coords, void* corr, int B, int H1,
                              int W1, int H2, int W2, int radius, int dtype, void* stream) {
   if (int rc = corr_check("corr_index_forward", B, 1, H1, W1, H2, W2, 1, radius, dtype)) return rc;
+  if (int rc = corr_map_check("corr_index_forward", H1, W1, H2, W2)) return rc;
   if (B == 0) return DROID_OK;
   if (!volume || !coords || !corr) return fail(DROID_E_ARG, "corr_index_forward: null %s", "pointer");
   int rc = launch_corr_index_forward(volume, coords, corr, B, H1, W1, H2, W2, radius, dtype,
@@ -102,6 +111,7 @@ int droid_corr_index_forward(const void* volume, const float* coords, void* corr
 int droid_corr_pyramid_forward(const void* const* volumes, const float* coords, void* corr, int B, int H1, int W1,
                                int radius, int levels, int dtype, void* stream) {
   if (B < 0 || H1 <= 0 || W1 <= 0 || levels < 1) return fail(DROID_E_ARG, "corr_pyramid_forward: bad %s", "shape");
+  if (int rc = corr_map_check("corr_pyramid_forward", H1, W1, H1, W1)) return rc;
   if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_pyramid_forward: bad %s", "dtype");
   if (B == 0) return DROID_OK;
   if (!volumes || !coords || !corr) return fail(DROID_E_ARG, "corr_pyramid_forward: null %s", "pointer");
@@ -143,6 +153,7 @@ int droid_corr_volume_pyramid(const void* fmaps, const int64_t* ii, const int64_
 int droid_corr_pyramid_forward_slots(const void* const* volumes, const int64_t* slots, const float* coords, void* corr,
                                      int B, int64_t cap, int H1, int W1, int radius, int levels, int dtype, void* stream) {
   if (B < 0 || B > 65535 || H1 <= 0 || W1 <= 0) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "shape");
+  if (int rc = corr_map_check("corr_pyramid_forward_slots", H1, W1, H1, W1)) return rc;
   if (dtype < DROID_F16 || dtype > DROID_F64) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "dtype");
   if (radius != 3 && radius != 4) return fail(DROID_E_ARG, "corr_pyramid_forward_slots: bad %s", "radius (3 or 4)");
   if (levels < 1 || levels > 8 || (H1 >> (levels - 1)) < 1 || (W1 >> (levels - 1)) < 1)
@@ -168,6 +179,7 @@ int droid_corr_volume_pyramid_slots(const void* fmaps, const int64_t* ii, const 
 int droid_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int B,
                               int H1, int W1, int H2, int W2, int radius, int dtype, void* stream) {
   if (int rc = corr_check("corr_index_backward", B, 1, H1, W1, H2, W2, 1, radius, dtype)) return rc;
+  if (int rc = corr_map_check("corr_index_backward", H1, W1, H2, W2)) return rc;
   if (B == 0) return DROID_OK;
   if (!coords || !corr_grad || !volume_grad) return fail(DROID_E_ARG, "corr_index_backward: null %s", "pointer");
   int rc = launch_corr_index_backward(coords, corr_grad, volume_grad, B, H1, W1, H2, W2, radius,

@@ -47,6 +47,12 @@ const char *droid_last_error(void); /* thread-local message of the last failing 
 
 /* ------------------------------------------------------------------ correlation lookups */
 
+/* Limits of the four volume operators below (droid_corr_index_forward / _backward, droid_corr_pyramid_forward and its
+ * _slots form): H1 * W1 <= 2^27 and H2 * W2 <= 2^27 (a query pixel index and the byte count of one plane are 32-bit),
+ * else DROID_E_ARG with a message that names the operator and "map size"; B <= 65535.  Offsets into the volumes and the
+ * outputs are 64-bit: B (or cap) * H1 * W1 * H2 * W2 may be any size the device holds (tests/test_gpu_large_offsets.py
+ * runs them beyond 2^32 elements and 8 GiB). */
+
 /* corr_index_forward (droid.cpp:170-178 -> correlation_kernels.cu:126-155).
  * volume [B,H1,W1,H2,W2] dtype ; coords [B,2,H1,W1] f32 ; corr [B,2r+1,2r+1,H1,W1] dtype
  * (written completely; the caller need not zero it). */

@@ -5,6 +5,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -133,3 +135,30 @@ def test_product_does_not_reference_the_oracle():
                 txt = open(os.path.join(dp, f), errors="replace").read()
                 assert "import oracle" not in txt and "from oracle" not in txt, os.path.join(dp, f)
                 assert "libdroid_oracle" not in txt, os.path.join(dp, f)
+
+
+@pytest.mark.parametrize("op", ["corr_index_forward", "corr_index_backward", "corr_pyramid_forward", "corr_pyramid_forward_slots"])
+def test_volume_operators_refuse_maps_their_32_bit_pixel_indices_cannot_hold(backends, op):
+    """H1 * W1 and H2 * W2 above 2^27 are refused by name before any pointer is looked at (a query pixel index and the
+    byte count of one plane are 32-bit; 46341^2 leaves int); 2^27 itself passes the size checks and fails on the null
+    pointers.  Offsets into the volumes are 64-bit: tests/test_gpu_large_offsets.py."""
+    lib = backends._lib.load()
+    levels = (ctypes.c_void_p * 1)(None)
+
+    def call(H1, W1, H2, W2):
+        if op == "corr_index_forward":
+            return lib.droid_corr_index_forward(None, None, None, 1, H1, W1, H2, W2, 3, 0, None)
+        if op == "corr_index_backward":
+            return lib.droid_corr_index_backward(None, None, None, 1, H1, W1, H2, W2, 3, 0, None)
+        if op == "corr_pyramid_forward":
+            return lib.droid_corr_pyramid_forward(levels, None, None, 1, H1, W1, 3, 1, 0, None)
+        return lib.droid_corr_pyramid_forward_slots(levels, None, None, None, 1, 4, H1, W1, 3, 1, 0, None)
+
+    shapes = [(46341, 46341, 1, 1), (1 << 14, (1 << 13) + 1, 1, 1)]
+    if op.startswith("corr_index"):
+        shapes += [(1, 1, 46341, 46341), (8, 8, (1 << 13) + 1, 1 << 14)]
+    for shape in shapes:
+        assert call(*shape) == -1
+        msg = lib.droid_last_error()
+        assert op.encode() in msg and b"map size" in msg, (shape, msg)
+    assert call(1 << 14, 1 << 13, 1, 1) == -1 and b"null" in lib.droid_last_error()
