@@ -30,6 +30,11 @@ __host__ __device__ inline size_t chol_tiles(int n) {
 __host__ __device__ inline size_t chol_mbuf_offset(int n) { return ((size_t)(n + CHOL_NB - 1) / CHOL_NB) * CHOL_NB * CHOL_NB; }
 __host__ __device__ inline size_t chol_lfin_offset(int n) { return 2 * chol_mbuf_offset(n); }
 __host__ __device__ inline size_t chol_ldiag_doubles(int n) { return chol_lfin_offset(n) + chol_tiles(n) * CHOL_NB * CHOL_NB; }
+// Back-substitution after a single-launch factorisation: workgroup J owns the block columns 2J and 2J+1 (the top one
+// a single column when their number is odd); x crosses a workgroup boundary once per pair.
+__host__ __device__ inline int chol_bs_pairs_grid(int nb) { return (nb + 1) / 2; }
+__host__ __device__ inline int chol_bs_pairs_owner(int col) { return col / 2; }
+__host__ __device__ inline int chol_bs_pairs_first(int wg) { return 2 * wg; }
 
 // Packed lower triangle + rhs row, BLOCK-COLUMN major (what the ranks all-reduce): block column J = columns
 // 64 J .. 64 J + w_J - 1 (w_J = 64, the last one n - 64 J) holds rows 64 J .. n (row n = rhs) as rows of w_J doubles.

@@ -22,7 +22,9 @@
 //     chain); `chol_step_kernel` (one launch per block column, same body) is the fallback;
 //   * `chol_factor_persistent_kernel<true>`: the same body and hand-off rules under a per-tile scheduler, for a system
 //     that arrives in column chunks while the kernel is running (multi-GPU overlap);
-//   * `chol_backsolve_persistent_kernel`: the backward substitution in one launch, x itself is the hand-off flag.
+//   * `chol_backsolve_persistent_kernel`: the backward substitution in one launch, x itself is the hand-off flag;
+//   * `chol_backsolve_pairs_kernel`: the same after a single-launch factorisation, two block columns per workgroup and
+//     nothing but mat-vecs behind the arrival of x (the default; DROID_CHOL_BS_PAIRS=0 selects the kernel above).
 #include <hip/hip_runtime.h>
 #include <mutex>
 
@@ -1400,11 +1402,327 @@ __global__ __launch_bounds__(256) void chol_backsolve_persistent_kernel(
   }
 }
 
+// ---- backward substitution, two block columns per workgroup ---------------------------------------------------
+// Workgroup J owns the block columns b = 2J and a = 2J+1 (chol_bs_pairs_*, ba_internal.hpp; with an odd number of block
+// columns the top workgroup owns one), so x crosses a workgroup boundary once per PAIR, 128 values at a time, with the
+// hand-off of the kernel above (x is its own flag, agent-scope 8-byte accesses, bounded polls).  With
+// N[r,c] = L[r,c] L_cc^-1 and u_c = L_cc^-T (y_c - sum_{k >= a+3} L[k,c]^T x_k), both finished before the newest x arrive,
+//   x_a = u_a - N[a+1,a]^T x_{a+1} - N[a+2,a]^T x_{a+2}
+//   x_b = u_b - N[a+1,b]^T x_{a+1} - N[a+2,b]^T x_{a+2} - N[a,b]^T x_a
+// leave nothing but mat-vecs behind the arrival of x_{a+1}, x_{a+2}: four tiles against the arrivals on eight waves
+// (32 rows of a tile each, their columns in registers before the poll returns), one barrier, one mat-vec for x_b.
+// N[c+1,c] is the factorisation's M buffer; the other three tiles of a pair are formed here, before the first poll, by the
+// right-to-left 16-column block substitution chol_tile uses for M, and stay in LDS.
+// Off the chain every wave keeps the sum of its own 32-row slices of L[k, a|b]^T x_k (k >= a+3, tile columns straight
+// from memory to registers: lane l reads L[r][c0 + l]) without any barrier; the eight sums meet once, before the solves.
+// `keep` is one 64-value register column per lane whose content depends on the wave's part after the far loop: column l
+// of L_cc and of its block inverses (waves 4, 5: the diagonal solves), of M_b (wave 6: the last mat-vec), or of a 32-row
+// half of M_a (waves 1, 3).
+#ifdef CHOL_STAMPS
+#define BS_STAMP_W(slot, wv) do { if (threadIdx.x == 64 * (wv) && blockIdx.x < 64) g_bs_stamps[blockIdx.x * 8 + (slot)] = wall_clock64(); } while (0)
+#else
+#define BS_STAMP_W(slot, wv) do { } while (0)
+#endif
+
+// 64x64 tile (row pitch `pitch`, rows >= rows_valid read 0) -> LDS by 512 threads, in two halves: the loads of everything
+// the set-up needs are in flight before the first LDS store waits for one
+struct BspTileRegs { f64x2 v[4]; };
+__device__ __forceinline__ BspTileRegs bsp_tile_issue(const gbl_f64* __restrict__ src, size_t pitch, int rows_valid) {
+  const int t = threadIdx.x;
+  BspTileRegs r;
+#pragma unroll
+  for (int it = 0; it < 4; it++) {
+    const int idx2 = it * 512 + t, i = idx2 >> 5, j = (idx2 & 31) * 2;
+    const bool ok = i < rows_valid;
+    r.v[it] = *(const gbl_f64x2*)(src + (ok ? (size_t)i * pitch + j : 0));
+    if (!ok) r.v[it] = (f64x2){0.0, 0.0};
+  }
+  return r;
+}
+__device__ __forceinline__ void bsp_tile_store(lds_f64* __restrict__ dst, const BspTileRegs& r) {
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < 4; it++) {
+    const int idx2 = it * 512 + t, i = idx2 >> 5, j = (idx2 & 31) * 2;
+    *(lds_f64x2*)(&dst[i * LDP + j]) = r.v[it];
+  }
+}
+
+// What the substitution below reads of a tile of `ldiag`, as ten 16x16 blocks of pitch 16: the blocks L_sq, s > q, at
+// s (s - 1) / 2 + q, and the inverse of the diagonal block q (kept in the tile's upper part) at 6 + q.
+constexpr int BSP_DC = 10 * 256;  // doubles
+// element pair e (< BSP_DC / 2) of that layout: its offset in the ldiag tile
+__device__ __forceinline__ int bsp_dc_source(int e) {
+  const int blk = e >> 7, i = (e & 127) >> 3, j = (e & 7) * 2;
+  int br, bc;
+  if (blk < 6) {
+    br = blk < 1 ? 1 : (blk < 3 ? 2 : 3);
+    bc = blk - br * (br - 1) / 2;
+  } else {
+    br = blk == 9 ? 1 : 0;
+    bc = blk == 9 ? 2 : blk - 5;
+  }
+  return (16 * br + i) * NB + 16 * bc + j;
+}
+
+// T <- T L_cc^-1 in place, rows 16 g .. 16 g + 15 by one wave: N_q = (T_q - sum_{s>q} N_s L_sq) L_qq^-1 for the 16-column
+// blocks q = 3 .. 0.  D = the blocks of L_cc and the inverses of its diagonal blocks, as bsp_dc_source lays them out.
+__device__ __forceinline__ void bsp_times_inverse(lds_f64* T, const lds_f64* D, int g, int lane) {
+  const int fr = lane & 15, fg = lane >> 4;
+#pragma unroll
+  for (int q = 3; q >= 0; q--) {
+    lds_f64* Cq = &T[(16 * g) * LDP + 16 * q];
+    f64x4 acc;
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[i] = Cq[(fg + 4 * i) * LDP + fr];
+#pragma unroll
+    for (int s2 = q + 1; s2 < 4; s2++)
+#pragma unroll
+      for (int kk = 0; kk < 16; kk += 4)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(-T[(16 * g + fr) * LDP + 16 * s2 + kk + fg],
+                                                   D[(s2 * (s2 - 1) / 2 + q) * 256 + (kk + fg) * 16 + fr], acc, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) Cq[(fg + 4 * i) * LDP + fr] = acc[i];  // back through LDS into the A-operand layout
+    f64x4 m = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kk = 0; kk < 16; kk += 4)
+      m = __builtin_amdgcn_mfma_f64_16x16x4f64(Cq[fr * LDP + kk + fg], D[(6 + q) * 256 + (kk + fg) * 16 + fr], m, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) Cq[(fg + 4 * i) * LDP + fr] = m[i];
+  }
+}
+
+// sum_r col[r] xs[r], r < NN, xs in 16-byte broadcast reads
+template <int NN>
+__device__ __forceinline__ double bsp_dot(const double* col, const lds_f64* xs) {
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+#pragma unroll
+  for (int r = 0; r < NN; r += 4) {
+    const f64x2 x01 = *(const lds_f64x2*)&xs[r], x23 = *(const lds_f64x2*)&xs[r + 2];
+    a0 = fma(col[r + 0], x01[0], a0);
+    a1 = fma(col[r + 1], x01[1], a1);
+    a2 = fma(col[r + 2], x23[0], a2);
+    a3 = fma(col[r + 3], x23[1], a3);
+  }
+  return (a0 + a1) + (a2 + a3);
+}
+
+__global__ __launch_bounds__(512) void chol_backsolve_pairs_kernel(
+    double* __restrict__ S_, int n, int ld, double* __restrict__ x, int* __restrict__ err,
+    const double* __restrict__ Ldiag_) {
+  __shared__ double Dc[2][BSP_DC];     // L_bb, L_aa: their blocks below the diagonal and the inverses of those on it
+  __shared__ double Nt[3][NB * LDP];   // N[a+2,a], N[a+1,b], N[a+2,b]
+  __shared__ double xs[8][NB];         // per wave: the x it polled (32 values; 64 for the last mat-vec) / the block solve
+  __shared__ double far_part[8][NB];   // per wave: its sum over the far tiles
+  __shared__ double near_part[8][NB];  // per wave: its 32-row slice against the arrivals
+  __shared__ double us[2][NB];         // u_b, u_a
+  __shared__ int dead;
+  const gbl_f64* const S = (const gbl_f64*)S_;
+  const gbl_f64* const Ldiag = (const gbl_f64*)Ldiag_;
+  const int t = threadIdx.x, w = t >> 6, l = t & 63;
+  const int nb = (n + NB - 1) / NB, G = gridDim.x, J = blockIdx.x;
+  const int b = chol_bs_pairs_first(J), a = b + 1;
+  const bool has_a = a < nb;         // false: the lone top column of an odd count
+  const bool above = a + 1 < nb;     // block rows above the pair: x arrives from workgroup J + 1
+  const bool above2 = a + 2 < nb;
+  const int ch = w & 1, rq = w >> 1;  // off-diagonal work: column b + ch, 32-row slice rq of a 128-row pair of block rows
+  lds_f64* const xw = DROID_LDS(xs[w]);
+  BS_STAMP_W(0, 0);
+  if (t == 0) dead = 0;
+
+  // ---- set-up loads: the tiles that become N first (they are waited for first), then the diagonal blocks ----
+  const int ra = (a + 1) * NB, rb = (a + 2) * NB;  // (rows from n on, the right-hand side among them, read 0)
+  BspTileRegs t0, t1, t2;
+  f64x2 dreg[5];
+  if (above) {
+    t1 = bsp_tile_issue(S + (size_t)ra * ld + (size_t)b * NB, ld, n - ra);
+    if (above2) {
+      t2 = bsp_tile_issue(S + (size_t)rb * ld + (size_t)b * NB, ld, n - rb);
+      t0 = bsp_tile_issue(S + (size_t)rb * ld + (size_t)a * NB, ld, n - rb);
+    }
+#pragma unroll
+    for (int it = 0; it < 5; it++) {  // 2 x BSP_DC / 2 pairs: L_bb's blocks, then L_aa's
+      const int idx2 = it * 512 + t, which = idx2 >= BSP_DC / 2 ? 1 : 0;
+      dreg[it] = *(const gbl_f64x2*)(Ldiag + (size_t)(b + which) * NB * NB + bsp_dc_source(idx2 - which * (BSP_DC / 2)));
+    }
+  }
+
+  // ---- the wave's register column ----
+  double keep[NB];
+  {
+    const gbl_f64* base = Ldiag;
+    int row_lo = 0, col_lo = l, row_hi = 0, used = 0;
+    if (w == 4 || (w == 5 && has_a)) {            // the diagonal solve of column b (wave 4) / a (wave 5)
+      const int pb = l >> 4;
+      base = Ldiag + (size_t)(b + w - 4) * NB * NB;
+      row_lo = pb == 3 ? 16 : 0;                  // [0..15]: (L_pp^-1)[c][l & 15] of this lane's diagonal block p
+      col_lo = 16 * (pb == 3 ? 2 : pb + 1) + (l & 15);
+      used = NB;
+    } else if (w == 6 && has_a) {                 // M_b = N[a,b]
+      base = Ldiag + chol_mbuf_offset(n) + (size_t)b * NB * NB;
+      used = NB;
+    } else if (ch == 1 && rq < 2 && above) {      // rows 32 rq .. of M_a = N[a+1,a] in [0..31]
+      base = Ldiag + chol_mbuf_offset(n) + (size_t)a * NB * NB;
+      row_lo = row_hi = 32 * rq;
+      used = 32;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; i++) {
+      keep[i] = 0.0;
+      if (i < used) keep[i] = base[(size_t)((i < 16 ? row_lo : row_hi) + i) * NB + (i < 16 ? col_lo : l)];
+    }
+  }
+  double z = 0.0;                                 // waves 4, 5: y_c
+  if ((w == 4 || (w == 5 && has_a)) && (b + w - 4) * NB + l < n) z = S[(size_t)n * ld + (b + w - 4) * NB + l];
+
+  // ---- the three N tiles of the pair: waves 0-3 N[a+1,b] then N[a+2,a], waves 4-7 N[a+2,b]; 16 rows of a tile are one
+  // wave's alone, so nothing but the barrier after the far loop stands between them and their readers ----
+  if (above) {
+    bsp_tile_store(DROID_LDS(Nt[1]), t1);
+    if (above2) {
+      bsp_tile_store(DROID_LDS(Nt[2]), t2);
+      bsp_tile_store(DROID_LDS(Nt[0]), t0);
+    }
+#pragma unroll
+    for (int it = 0; it < 5; it++) *(lds_f64x2*)&DROID_LDS(Dc[0])[2 * (it * 512 + t)] = dreg[it];
+    __syncthreads();
+    if (w < 4) {
+      bsp_times_inverse(DROID_LDS(Nt[1]), DROID_LDS(Dc[0]), w, l);
+      if (above2) bsp_times_inverse(DROID_LDS(Nt[0]), DROID_LDS(Dc[1]), w, l);
+    } else if (above2) {
+      bsp_times_inverse(DROID_LDS(Nt[2]), DROID_LDS(Dc[0]), w - 4, l);
+    }
+  }
+  BS_STAMP_W(1, 0);
+
+  // the lanes' elements of x from `gi` on (lanes beyond `lanes` and beyond the matrix take 0), as soon as they are there
+  auto poll = [&](int gi, int lanes) -> double {
+    double xv = 0.0;
+    if (l < lanes && gi + l < n) {
+      int spins = 0;
+      while (true) {
+        xv = __hip_atomic_load(&x[gi + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__double_as_longlong(xv) != BSP_SENTINEL) break;
+        if (++spins > (1 << 22)) {  // cannot happen with a resident grid; never hang the GPU
+          *(volatile int*)&dead = 1;
+          atomicMax(err, 2);
+          xv = 0.0;
+          break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+      }
+    }
+    return xv;
+  };
+
+  // ---- off the chain: the pairs of block rows from a+3 on, as workgroups G-1 .. J+2 publish them ----
+  double far = 0.0;
+  for (int P = G - 1; P >= J + 2; P--) {
+    if (*(volatile int*)&dead) break;
+    const int r0 = 2 * P * NB + 32 * rq;
+    const gbl_f64* col = S + (size_t)(b + ch) * NB + l;
+    double Tc[32];
+#pragma unroll
+    for (int r = 0; r < 32; r++) {
+      const int row = r0 + r;
+      Tc[r] = col[(size_t)(row < n ? row : n - 1) * ld];
+      if (row >= n) Tc[r] = 0.0;
+    }
+    const double xv = poll(r0, 32);
+    if (l < 32) xw[l] = xv;  // same wave writes and reads: LDS operations of one wave are ordered
+    far += bsp_dot<32>(Tc, xw);
+  }
+  DROID_LDS(far_part[w])[l] = far;
+  BS_STAMP_W(2, 0);
+  __syncthreads();
+  if (dead) return;
+
+  // ---- u_c = L_cc^-T z_c, 16 unknowns at a time with the block inverses (as the kernel above) ----
+  if (w == 4 || (w == 5 && has_a)) {
+    const int c = w - 4;
+    z -= (far_part[c][l] + far_part[2 + c][l]) + (far_part[4 + c][l] + far_part[6 + c][l]);
+    const int rowb = l >> 4;
+    double xsol = 0.0;
+#define DROID_BSP_WTERM(ACC, C)                                                                         \
+    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #C " row_mask:0xf bank_mask:0xf"             \
+                 : "+v"(ACC) : "v"(z), "v"(keep[C]));
+#define DROID_BSP_BLOCK(B)                                                                              \
+    if (rowb == B) {                                                                                   \
+      double xw0 = 0.0, xw1 = 0.0;                                                                     \
+      asm volatile("s_nop 1" : "+v"(z));                                                               \
+      DROID_BSP_WTERM(xw0, 0) DROID_BSP_WTERM(xw1, 1) DROID_BSP_WTERM(xw0, 2) DROID_BSP_WTERM(xw1, 3)  \
+      DROID_BSP_WTERM(xw0, 4) DROID_BSP_WTERM(xw1, 5) DROID_BSP_WTERM(xw0, 6) DROID_BSP_WTERM(xw1, 7)  \
+      DROID_BSP_WTERM(xw0, 8) DROID_BSP_WTERM(xw1, 9) DROID_BSP_WTERM(xw0, 10) DROID_BSP_WTERM(xw1, 11) \
+      DROID_BSP_WTERM(xw0, 12) DROID_BSP_WTERM(xw1, 13) DROID_BSP_WTERM(xw0, 14) DROID_BSP_WTERM(xw1, 15) \
+      xsol = xw0 + xw1;                                                                                \
+      xw[l] = xsol;                                                                                    \
+    }                                                                                                  \
+    if (B > 0 && rowb < B) {                                                                           \
+      double u0 = 0.0, u1 = 0.0;                                                                       \
+      _Pragma("unroll") for (int ii = 0; ii < 16; ii += 2) {                                           \
+        const f64x2 xx = *(const lds_f64x2*)&xw[16 * B + ii];                                           \
+        u0 = fma(keep[16 * B + ii], xx[0], u0);                                                        \
+        u1 = fma(keep[16 * B + ii + 1], xx[1], u1);                                                    \
+      }                                                                                                \
+      z -= u0 + u1;                                                                                    \
+    }
+    DROID_BSP_BLOCK(3)
+    DROID_BSP_BLOCK(2)
+    DROID_BSP_BLOCK(1)
+    DROID_BSP_BLOCK(0)
+#undef DROID_BSP_BLOCK
+#undef DROID_BSP_WTERM
+    DROID_LDS(us[c])[l] = xsol;
+    BS_STAMP_W(3, 4);
+  }
+
+  // ---- on the chain: x_{a+1}, x_{a+2} arrive together ----
+  double near = 0.0;
+  if (above && (rq < 2 || above2)) {
+    double Nc[32];  // rows 32 (rq & 1) .. of N[a+1 + (rq >> 1), b + ch], column l
+    if (ch == 1 && rq < 2) {
+#pragma unroll
+      for (int r = 0; r < 32; r++) Nc[r] = keep[r];
+    } else {
+      const lds_f64* T = DROID_LDS(ch == 1 ? Nt[0] : (rq < 2 ? Nt[1] : Nt[2])) + (32 * (rq & 1)) * LDP + l;
+#pragma unroll
+      for (int r = 0; r < 32; r++) Nc[r] = T[r * LDP];
+    }
+    const double xv = poll((a + 1) * NB + 32 * rq, 32);
+    BS_STAMP_W(4, 0);
+    if (l < 32) xw[l] = xv;
+    near = bsp_dot<32>(Nc, xw);
+  }
+  DROID_LDS(near_part[w])[l] = near;
+  __syncthreads();
+  if (dead) return;
+  BS_STAMP_W(5, 6);
+  if (w == 6 || (w == 7 && has_a)) {
+    const auto publish = [&](int c0, double v) {
+      if (__double_as_longlong(v) == BSP_SENTINEL) v = __longlong_as_double(0x7ff8000000000000LL);
+      if (c0 + l < n) __hip_atomic_store(&x[c0 + l], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    double xb = us[0][l] - ((near_part[0][l] + near_part[2][l]) + (near_part[4][l] + near_part[6][l]));
+    if (has_a) {
+      const double xa = us[1][l] - ((near_part[1][l] + near_part[3][l]) + (near_part[5][l] + near_part[7][l]));
+      if (w == 7) {
+        publish(a * NB, xa);
+        return;
+      }
+      xw[l] = (a * NB + l < n) ? xa : 0.0;
+      xb -= bsp_dot<NB>(keep, xw);
+    }
+    BS_STAMP_W(6, 6);
+    publish(b * NB, xb);
+    BS_STAMP_W(7, 6);
+  }
+}
+
 // ---- host side: the launchers of a CholSystem (ba_internal.hpp) ------------------------------------------------
 // launch_chol_factor: the step-major single-launch kernel where chol_single_launch allows it, else one chol_step_kernel
 // per block column.  launch_chol_factor_overlap: the per-tile single-launch kernel or nothing.  launch_chol_backsolve:
-// the persistent kernel for 2 .. BSP_MAX_BLOCKS block columns (FAST after a single-launch factorisation: it reads
-// L_jj from `ldiag`), else one chol_backsolve_kernel per block column, which reads L_jj from the matrix: after a
+// a persistent kernel for 2 .. BSP_MAX_BLOCKS block columns (after a single-launch factorisation the paired one, or with
+// DROID_CHOL_BS_PAIRS=0 the FAST instantiation of the per-column one: both read L_jj from `ldiag`), else one chol_backsolve_kernel per block column, which reads L_jj from the matrix: after a
 // single-launch factorisation chol_ldiag_to_sys_kernel first copies them back.  Spinning grids: launch_spinning_grid.
 // Diagnostic and test switches of the solver; every variable is read once per process.
 struct CholSwitches {
@@ -1413,13 +1731,14 @@ struct CholSwitches {
   bool force_bs_refusal;   // DROID_CHOL_FORCE_BS_REFUSAL: the cooperative back-substitution counts as refused
   int grid;                // DROID_CHOL_GRID: cap of the factorisation grid (taken when >= 8 and below the residency)
   int overlap_reserve;     // DROID_OVERLAP_RESERVE_CUS (default 32): CUs the overlap factorisation leaves free
+  bool bs_pairs;           // DROID_CHOL_BS_PAIRS=0: the FAST back-substitution with one block column per workgroup
 };
 static const CholSwitches& chol_switches() {
   const auto is_set = [](const char* name) { return getenv(name) != nullptr; };
   const auto number = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
   static const CholSwitches sw = {is_set("DROID_CHOL_MULTI_LAUNCH"), number("DROID_CHOL_COOPERATIVE", 0) != 0,
                                   is_set("DROID_CHOL_FORCE_BS_REFUSAL"), number("DROID_CHOL_GRID", 0),
-                                  number("DROID_OVERLAP_RESERVE_CUS", 32)};
+                                  number("DROID_OVERLAP_RESERVE_CUS", 32), number("DROID_CHOL_BS_PAIRS", 1) != 0};
   return sw;
 }
 
@@ -1556,16 +1875,26 @@ bool launch_chol_factor(const CholSystem& c, double lm, double ep, hipStream_t s
   return false;
 }
 
+// The pairing as the launcher and the kernel use it (tests/test_gpu_backsolve_pairs.py holds it against a restatement):
+// owner[j] = workgroup of block column j, j < nb; returns the grid size.
+extern "C" int droid_debug_bs_pairs_map(int nb, int* owner) {
+  for (int j = 0; j < nb; j++) owner[j] = chol_bs_pairs_owner(j);
+  return chol_bs_pairs_grid(nb);
+}
+
 void launch_chol_backsolve(const CholSystem& c, bool factor_single, hipStream_t s) {
   const int nb = (c.n + NB - 1) / NB;
   if (nb >= 2 && nb <= BSP_MAX_BLOCKS) {
     CholSystem a = c;
     const double* ld_arg = factor_single ? c.ldiag : nullptr;
     void* args[] = {&a.S, &a.n, &a.ld, &a.x, &a.fail, &ld_arg};
-    const void* fn = factor_single ? (const void*)chol_backsolve_persistent_kernel<true>
+    const bool pairs = factor_single && chol_switches().bs_pairs;  // two block columns per workgroup, eight waves
+    const void* fn = pairs ? (const void*)chol_backsolve_pairs_kernel
+                   : factor_single ? (const void*)chol_backsolve_persistent_kernel<true>
                                    : (const void*)chol_backsolve_persistent_kernel<false>;
     // refused: the per-step kernels below (`x` carries the sentinel preset, they overwrite all of it)
-    if (launch_spinning_grid(fn, nb, 256, args, s, chol_switches().force_bs_refusal)) return;
+    if (launch_spinning_grid(fn, pairs ? chol_bs_pairs_grid(nb) : nb, pairs ? 512 : 256, args, s,
+                             chol_switches().force_bs_refusal)) return;
   }
   if (factor_single)
     hipLaunchKernelGGL(chol_ldiag_to_sys_kernel, dim3(nb), dim3(256), 0, s, c.S, c.n, c.ld, c.ldiag);
