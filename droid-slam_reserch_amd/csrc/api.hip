@@ -10,6 +10,7 @@
 
 #include "../../include/droid_backends_hip.h"
 #include "../../include/droid_test_hooks_hip.h"
+#include "../../include/droid_motion_encode_hip.h"
 #include "../../include/droid_update_hip.h"
 #include "ba_internal.hpp"
 #include "graph.hpp"
@@ -965,6 +966,28 @@ int droid_corr_encode(const void* const* volumes, const int64_t* slots, const fl
                               coords_layout == DROID_COORDS_HW2, (hipStream_t)stream);
   if (rc) return fail(rc, "corr_encode: %s", "unsupported configuration");
   return check_hip("corr_encode");
+}
+
+// ---------------------------------------------------------------------------- motion_encode (droid_motion_encode_hip.h)
+size_t droid_motion_encode_packed_bytes(void) { return DROID_CORR_ENCODE_PACKED_BYTES; }
+
+int droid_motion_encode(const float* poses, const float* disps, const float* intrinsics, int intr_stride, const int64_t* ii,
+                        const int64_t* jj, const float* target, const float* motn_in, const void* packed, float* coords,
+                        float* valid, void* out, int E, int nbuf, int H, int W, int out_channels, void* stream) {
+  if (E < 0 || E > 65535) return fail(DROID_E_ARG, "motion_encode: bad %s", "E (0 .. 65535)");
+  if (H < 1 || W < 1 || (int64_t)H * W > ((int64_t)1 << 30))
+    return fail(DROID_E_ARG, "motion_encode: bad %s", "map size (H, W >= 1, H * W <= 2^30)");
+  if (nbuf < 1) return fail(DROID_E_ARG, "motion_encode: bad %s", "nbuf (at least 1)");
+  if (out_channels != 128) return fail(DROID_E_ARG, "motion_encode: bad %s", "out_channels (128)");
+  if (intr_stride != 0 && intr_stride != 4) return fail(DROID_E_ARG, "motion_encode: bad %s", "intr_stride (0 or 4)");
+  if (E == 0) return DROID_OK;
+  if (!packed || !out) return fail(DROID_E_ARG, "motion_encode: null %s", "pointer (packed, out)");
+  if (((uintptr_t)packed & 15) != 0) return fail(DROID_E_ARG, "motion_encode: %s", "packed is not 16-byte aligned");
+  if (!motn_in && (!poses || !disps || !intrinsics || !ii || !jj || !target || !coords || !valid))
+    return fail(DROID_E_ARG, "motion_encode: null %s", "pointer (the geometry source and coords, valid, or motn_in)");
+  launch_motion_encode(poses, disps, intrinsics, intr_stride, ii, jj, target, motn_in, packed, coords, valid, out, E, nbuf, H,
+                       W, (hipStream_t)stream);
+  return check_hip("motion_encode");
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "../../include/droid_backends_hip.h"
+#include "encode_tile.hpp"
 #include "launchers.hpp"
 
 // The rounding points are part of the contract: no fused multiply-add and no mixed-precision
@@ -721,11 +722,6 @@ int launch_corr_pyramid_forward_slots(const void* const* volumes, const int64_t*
 // t takes as its row r the pixel 16 (r >> 2) + 4 t + (r & 3), so that a lane's 16 accumulator elements of one channel are
 // 16 CONSECUTIVE pixels: the epilogue (bias, one rounding to half, max with 0) stores them with two 16-byte stores, and
 // the four lanes of a channel cover the wave's 64 pixels as one contiguous 128-byte segment.
-constexpr int CE_LEVELS = 4, CE_R = 3, CE_K = 49, CE_KP = 64, CE_N = 128, CE_PITCH = 72;
-static_assert(CE_K == (2 * CE_R + 1) * (2 * CE_R + 1) && CE_K <= CE_KP && CE_KP + 8 == CE_PITCH, "A tile: 49 of 64 columns");
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct TileDst {
   _Float16* row;  // the lane's row of the A tile
   __device__ __forceinline__ void put(int k, float v) const {  // fp32 pyramids: the autocast cast, nearest-even, overflow to inf
@@ -739,36 +735,6 @@ template <typename T>
 struct EncodeLevels {
   const T* v[CE_LEVELS];
 };
-
-// epilogue of one channel tile: lane (g, c16) holds, for channel n, the pixels p0 + 4 t + i in acc[t][i]
-__device__ __forceinline__ void ce_store(const f32x4 (&acc)[4], int n, const __half* __restrict__ b16, __half* __restrict__ y,
-                                         int b, int H1W1, int p0, bool wide) {
-  const float bias = __half2float(b16[n]);
-  __half* o = y + ((size_t)b * CE_N + n) * H1W1 + p0;
-  unsigned short h[16];
-#pragma unroll
-  for (int t = 0; t < 4; t++)
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const __half r = __float2half_rn(acc[t][i] + bias);
-      const float rf = __half2float(r);
-      // max(., 0) that keeps a NaN: +0 for everything that is not above zero
-      h[4 * t + i] = (rf > 0.f || rf != rf) ? __half_as_ushort(r) : (unsigned short)0;
-    }
-  if (wide) {
-    uint4 v0, v1;
-    v0.x = h[0] | ((uint32_t)h[1] << 16); v0.y = h[2] | ((uint32_t)h[3] << 16);
-    v0.z = h[4] | ((uint32_t)h[5] << 16); v0.w = h[6] | ((uint32_t)h[7] << 16);
-    v1.x = h[8] | ((uint32_t)h[9] << 16); v1.y = h[10] | ((uint32_t)h[11] << 16);
-    v1.z = h[12] | ((uint32_t)h[13] << 16); v1.w = h[14] | ((uint32_t)h[15] << 16);
-    reinterpret_cast<uint4*>(o)[0] = v0;
-    reinterpret_cast<uint4*>(o)[1] = v1;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 16; k++)
-      if (p0 + k < H1W1) o[k] = __ushort_as_half(h[k]);
-  }
-}
 
 // Two waves per SIMD (219 / 238 VGPRs for half / fp32 pyramids, accumulators included): without the attribute the
 // compiler spreads over 146 + 128 registers and one wave per SIMD is left to hide the gather's latency
@@ -801,7 +767,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void co
     *reinterpret_cast<uint4*>(row + 56) = z;
   }
   const int g = lane >> 4, c16 = lane & 15;
-  const int arow = 16 * (c16 >> 2) + (c16 & 3);  // + 4 t: the pixel that is row c16 of MFMA tile t
+  const int arow = ce_arow(c16);
   f32x4 acc[8][4];  // [channel tile][pixel tile]
 #pragma unroll
   for (int nt = 0; nt < 8; nt++)
@@ -821,20 +787,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void co
     if (l > 0) __syncthreads();  // the previous level's fragments have been read
     q.combine_to(tap, TileDst{row});
     __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-      f16x8 a[4];
-#pragma unroll
-      for (int t = 0; t < 4; t++)
-        a[t] = *reinterpret_cast<const f16x8*>(tile + (arow + 4 * t) * CE_PITCH + s * 32 + g * 8);
-      const f16x8* wl = wpk + ((size_t)(l * 2 + s) * 8) * 64 + lane;
-#pragma unroll
-      for (int nt = 0; nt < 8; nt++) {
-        const f16x8 bf = wl[nt * 64];
-#pragma unroll
-        for (int t = 0; t < 4; t++) acc[nt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], bf, acc[nt][t], 0, 0, 0);
-      }
-    }
+    ce_mma(tile, wpk, l, lane, g, arow, acc);
   }
   const int p0 = pix0 + 16 * g;
   const bool wide = (H1W1 & 7) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && p0 + 16 <= H1W1;

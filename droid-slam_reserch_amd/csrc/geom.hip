@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "launchers.hpp"
+#include "reproject_pixel.hpp"
 #include "se3.hpp"
 
 namespace droid {
@@ -190,13 +191,8 @@ __global__ __launch_bounds__(256) void projmap_kernel(
 }
 
 
-// reproject + motion features of the update operator, one pass:
-//   depth_video.py:150-158 `reproject` -> geom/projective_ops.py:96-125 `projective_transform`
-//   (back-projection with the SOURCE frame's intrinsics :99, Gij = Gj * Gi^-1 :102, stereo edges ii == jj use
-//   the fixed baseline (-0.1, 0, 0) :105, projection with the TARGET frame's intrinsics where a depth below
-//   0.5 * MIN_DEPTH is replaced by 1 :46-51, valid = depth > MIN_DEPTH = 0.2 :113 -- these are the Python-side
-//   constants, not the 0.25 of droid_kernels.cu), then factor_graph.py:203-205:
-//   motn = clamp(cat(coords1 - coords0, target - coords1), -64, 64) laid out [E,4,H,W].
+// reproject + motion features of the update operator, one pass (reproject_pixel.hpp: the arithmetic and its sources),
+// motn laid out [E,4,H,W].
 // One thread per pixel; coords/valid/motn rows are written with unit stride (motn planes are H*W apart).
 __global__ __launch_bounds__(256) void reproject_motion_kernel(
     const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intrinsics,
@@ -216,27 +212,20 @@ __global__ __launch_bounds__(256) void reproject_motion_kernel(
       for (int c = 0; c < 4; c++) motn[((size_t)e * 4 + c) * HW + k] = 0.f;
     return;
   }
-  const float* ki = intrinsics + (size_t)i64 * intr_stride;
-  const float* kj = intrinsics + (size_t)j64 * intr_stride;
-  const Intr Ki = {ki[0], ki[1], ki[2], ki[3]};
-  const Rel T = rel_pose<true>(poses, (int)i64, (int)j64);
+  const ReprojEdge g = reproject_edge(poses, intrinsics, intr_stride, i64, j64);
   const float u = (float)(k % W), v = (float)(k / W);
-  float Xj[4];
-  transform_pixel(Ki, T, u, v, disps[(size_t)i64 * HW + k], Xj);
-  const float Z = Xj[2];
-  const float d = 1.0f / ((Z < 0.5f * 0.2f) ? 1.0f : Z);
-  const float x = kj[0] * (Xj[0] * d) + kj[2];
-  const float y = kj[1] * (Xj[1] * d) + kj[3];
-  reinterpret_cast<float2*>(coords)[o] = make_float2(x, y);
-  valid[o] = (Z > 0.2f) ? 1.0f : 0.0f;  // the source point has depth 1 > MIN_DEPTH by construction
+  float vl;
+  const float2 xy = reproject_pixel(g, u, v, disps[(size_t)i64 * HW + k], vl);
+  reinterpret_cast<float2*>(coords)[o] = xy;
+  valid[o] = vl;
   if (motn) {
-    const float2 tg = reinterpret_cast<const float2*>(target)[o];
-    auto clamp64 = [](float a) { return fminf(fmaxf(a, -64.0f), 64.0f); };
+    float mp[4];
+    motion_pixel(xy, u, v, reinterpret_cast<const float2*>(target)[o], mp);
     float* m = motn + (size_t)e * 4 * HW + k;
-    m[0] = clamp64(x - u);
-    m[HW] = clamp64(y - v);
-    m[2 * (size_t)HW] = clamp64(tg.x - x);
-    m[3 * (size_t)HW] = clamp64(tg.y - y);
+    m[0] = mp[0];
+    m[HW] = mp[1];
+    m[2 * (size_t)HW] = mp[2];
+    m[3 * (size_t)HW] = mp[3];
   }
 }
 

@@ -48,6 +48,10 @@ void launch_iproj(const float* poses, const float* disps, const float* intr, int
 void launch_depth_filter(const float* poses, const float* disps, const float* intr,
                          const int64_t* ix, const float* thresh, int num, int nbuf, int H, int W,
                          float* counter, hipStream_t s);
+// motion_encode.hip
+void launch_motion_encode(const float* poses, const float* disps, const float* intr, int intr_stride, const int64_t* ii,
+                          const int64_t* jj, const float* target, const float* motn_in, const void* packed, float* coords,
+                          float* valid, void* out, int E, int nbuf, int H, int W, hipStream_t s);
 // upsample.hip
 void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
                          bool half_mask, hipStream_t s);

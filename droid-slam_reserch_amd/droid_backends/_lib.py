@@ -82,6 +82,13 @@ ABI_CORR_ENCODE = {
     "droid_corr_encode": ("i", "P 4p i l 7i p"),
 }
 SYMBOLS_CORR_ENCODE = list(ABI_CORR_ENCODE)
+# include/droid_motion_encode_hip.h, contract and prototypes (tests/test_motion_encode_abi.py holds the table against
+# them).  A table of its own for the same reason: tests/test_corr_encode_abi.py pins ABI_CORR_ENCODE at its two entries.
+ABI_MOTION_ENCODE = {
+    "droid_motion_encode_packed_bytes": ("z", ""),
+    "droid_motion_encode": ("i", "3p i 8p 5i p"),
+}
+SYMBOLS_MOTION_ENCODE = list(ABI_MOTION_ENCODE)
 # The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
 # A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
 # prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
@@ -97,8 +104,8 @@ _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": cty
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE or ABI_TEST as ctypes types."""
-    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE):
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE or ABI_TEST as ctypes types."""
+    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE):
         if name in table:
             break
     else:
@@ -127,7 +134,7 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_TEST:
+    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_TEST:
         if not hasattr(lib, s):
             if s in SYMBOLS_TEST:
                 continue
