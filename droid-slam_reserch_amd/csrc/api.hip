@@ -10,6 +10,7 @@
 
 #include "../../include/droid_backends_hip.h"
 #include "../../include/droid_test_hooks_hip.h"
+#include "../../include/droid_heads_hip.h"
 #include "../../include/droid_motion_encode_hip.h"
 #include "../../include/droid_update_hip.h"
 #include "ba_internal.hpp"
@@ -988,6 +989,35 @@ int droid_motion_encode(const float* poses, const float* disps, const float* int
   launch_motion_encode(poses, disps, intrinsics, intr_stride, ii, jj, target, motn_in, packed, coords, valid, out, E, nbuf, H,
                        W, (hipStream_t)stream);
   return check_hip("motion_encode");
+}
+
+// ---------------------------------------------------------------------------- update_heads (droid_heads_hip.h)
+size_t droid_head_packed_bytes(int n_out) {
+  if (n_out != 1 && n_out != 2) return 0;
+  return (((size_t)(1152 + 1) * n_out * sizeof(float)) + 15) / 16 * 16;
+}
+
+int droid_update_heads(const void* const* x, const void* const* packed, void* const* out, const int* n_out, const int* act,
+                       int heads, int B, int H, int W, int in_channels, void* stream) {
+  if (heads != 1 && heads != 2) return fail(DROID_E_ARG, "update_heads: bad %s", "heads (1 or 2)");
+  if (B < 0 || B > 65535) return fail(DROID_E_ARG, "update_heads: bad %s", "B (0 .. 65535)");
+  if (H < 1 || W < 1 || (int64_t)H * W > ((int64_t)1 << 30))
+    return fail(DROID_E_ARG, "update_heads: bad %s", "map size (H, W >= 1, H * W <= 2^30)");
+  if (in_channels != 128) return fail(DROID_E_ARG, "update_heads: bad %s", "in_channels (128)");
+  for (int k = 0; n_out && k < heads; k++)
+    if (n_out[k] != 1 && n_out[k] != 2) return fail(DROID_E_ARG, "update_heads: bad %s", "n_out (1 or 2)");
+  for (int k = 0; act && k < heads; k++)
+    if (act[k] < DROID_HEAD_IDENTITY || act[k] > DROID_HEAD_SOFTPLUS_CENTI)
+      return fail(DROID_E_ARG, "update_heads: bad %s", "act (DROID_HEAD_IDENTITY, _SIGMOID or _SOFTPLUS_CENTI)");
+  if (B == 0) return DROID_OK;
+  if (!x || !packed || !out || !n_out || !act)
+    return fail(DROID_E_ARG, "update_heads: null %s", "pointer (x, packed, out, n_out, act)");
+  for (int k = 0; k < heads; k++)
+    if (!x[k] || !packed[k] || !out[k]) return fail(DROID_E_ARG, "update_heads: null %s", "pointer (an entry of x, packed, out)");
+  for (int k = 0; k < heads; k++)
+    if (((uintptr_t)packed[k] & 15) != 0) return fail(DROID_E_ARG, "update_heads: %s", "packed is not 16-byte aligned");
+  launch_update_heads(x, packed, out, n_out, act, heads, B, H, W, (hipStream_t)stream);
+  return check_hip("update_heads");
 }
 
 }  // extern "C"

@@ -52,6 +52,9 @@ void launch_depth_filter(const float* poses, const float* disps, const float* in
 void launch_motion_encode(const float* poses, const float* disps, const float* intr, int intr_stride, const int64_t* ii,
                           const int64_t* jj, const float* target, const float* motn_in, const void* packed, float* coords,
                           float* valid, void* out, int E, int nbuf, int H, int W, hipStream_t s);
+// heads.hip
+void launch_update_heads(const void* const* x, const void* const* packed, void* const* out, const int* n_out,
+                         const int* act, int heads, int B, int H, int W, hipStream_t s);
 // upsample.hip
 void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
                          bool half_mask, hipStream_t s);

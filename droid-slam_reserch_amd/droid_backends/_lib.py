@@ -89,6 +89,14 @@ ABI_MOTION_ENCODE = {
     "droid_motion_encode": ("i", "3p i 8p 5i p"),
 }
 SYMBOLS_MOTION_ENCODE = list(ABI_MOTION_ENCODE)
+# include/droid_heads_hip.h, contract and prototypes (tests/test_update_heads_abi.py holds the table against them).  A
+# table of its own once more: tests/test_motion_encode_abi.py pins ABI_MOTION_ENCODE at its two entries.  The arrays of
+# a call are "P" (the pointers of the heads) and "I" (n_out, act: one int per head).
+ABI_HEADS = {
+    "droid_head_packed_bytes": ("z", "i"),
+    "droid_update_heads": ("i", "3P 2I 5i p"),
+}
+SYMBOLS_HEADS = list(ABI_HEADS)
 # The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
 # A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
 # prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
@@ -104,8 +112,9 @@ _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": cty
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE or ABI_TEST as ctypes types."""
-    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE):
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS or ABI_TEST as ctypes
+    types."""
+    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS):
         if name in table:
             break
     else:
@@ -134,7 +143,7 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_TEST:
+    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_HEADS + SYMBOLS_TEST:
         if not hasattr(lib, s):
             if s in SYMBOLS_TEST:
                 continue
