@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/droid_backends_hip.h"
+#include "../../include/droid_conv3x3_hip.h"
 #include "../../include/droid_test_hooks_hip.h"
 #include "../../include/droid_heads_hip.h"
 #include "../../include/droid_motion_encode_hip.h"
@@ -1018,6 +1019,40 @@ int droid_update_heads(const void* const* x, const void* const* packed, void* co
     if (((uintptr_t)packed[k] & 15) != 0) return fail(DROID_E_ARG, "update_heads: %s", "packed is not 16-byte aligned");
   launch_update_heads(x, packed, out, n_out, act, heads, B, H, W, (hipStream_t)stream);
   return check_hip("update_heads");
+}
+
+// ---------------------------------------------------------------------------- conv3x3 (droid_conv3x3_hip.h)
+static bool conv3x3_sizes(int c_in, int c_out) {
+  return c_in >= 32 && c_in <= 512 && c_in % 32 == 0 && c_out >= 64 && c_out <= 256 && c_out % 64 == 0;
+}
+
+size_t droid_conv3x3_packed_bytes(int c_in, int c_out) {
+  if (!conv3x3_sizes(c_in, c_out)) return 0;
+  return ((size_t)9 * c_in * c_out + c_out) * 2;
+}
+
+int droid_conv3x3(const void* x, const void* packed, void* y, int B, int c_in, int c_out, int H, int W,
+                  int64_t x_batch_stride, int64_t y_batch_stride, int64_t y_group_stride, int group_channels, int relu,
+                  void* stream) {
+  if (B < 0 || B > 65535) return fail(DROID_E_ARG, "conv3x3: bad %s", "B (0 .. 65535)");
+  if (c_in < 32 || c_in > 512 || c_in % 32 != 0) return fail(DROID_E_ARG, "conv3x3: bad %s", "c_in (a multiple of 32 in 32 .. 512)");
+  if (c_out < 64 || c_out > 256 || c_out % 64 != 0)
+    return fail(DROID_E_ARG, "conv3x3: bad %s", "c_out (a multiple of 64 in 64 .. 256)");
+  if (H < 1 || W < 1 || (int64_t)H * W > ((int64_t)1 << 30))
+    return fail(DROID_E_ARG, "conv3x3: bad %s", "map size (H, W >= 1, H * W <= 2^30)");
+  if (group_channels < 64 || group_channels % 64 != 0 || c_out % group_channels != 0)
+    return fail(DROID_E_ARG, "conv3x3: bad %s", "group_channels (a multiple of 64 that divides c_out)");
+  if (relu != 0 && relu != 1) return fail(DROID_E_ARG, "conv3x3: bad %s", "relu (0 or 1)");
+  const int64_t HW = (int64_t)H * W;
+  if (B > 1 && x_batch_stride < c_in * HW) return fail(DROID_E_ARG, "conv3x3: bad %s", "x_batch_stride (below c_in * H * W)");
+  if (B > 1 && y_batch_stride < group_channels * HW)
+    return fail(DROID_E_ARG, "conv3x3: bad %s", "y_batch_stride (below group_channels * H * W)");
+  if (B == 0) return DROID_OK;
+  if (!x || !packed || !y) return fail(DROID_E_ARG, "conv3x3: null %s", "pointer (x, packed, y)");
+  if (((uintptr_t)packed & 15) != 0) return fail(DROID_E_ARG, "conv3x3: %s", "packed is not 16-byte aligned");
+  launch_conv3x3(x, packed, y, B, c_in, c_out, H, W, x_batch_stride, y_batch_stride, y_group_stride, group_channels, relu,
+                 (hipStream_t)stream);
+  return check_hip("conv3x3");
 }
 
 }  // extern "C"

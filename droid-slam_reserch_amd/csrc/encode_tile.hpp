@@ -7,7 +7,8 @@
 // [4 groups][2 K steps][8 channel tiles][64 lanes][8], then b16 [128].  MFMA tile t takes as its row r the pixel
 // 16 (r >> 2) + 4 t + (r & 3), so that a lane's 16 accumulator elements of one channel are 16 CONSECUTIVE pixels: the
 // epilogue (bias, one rounding to half, max with 0) stores them with two 16-byte stores, and the four lanes of a channel
-// cover the wave's 64 pixels as one contiguous 128-byte segment.
+// cover the wave's 64 pixels as one contiguous 128-byte segment.  conv3x3_kernel (conv3x3.hip) takes the types, the row
+// mapping (ce_arow) and the epilogue with an address of its own (ce_store_run); its tile and weight layout are its own.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -71,6 +72,36 @@ __device__ __forceinline__ void ce_store(const f32x4 (&acc)[4], int n, const __h
 #pragma unroll
     for (int k = 0; k < 16; k++)
       if (p0 + k < H1W1) o[k] = __ushort_as_half(h[k]);
+  }
+}
+
+// ce_store's sibling for a caller with its own addressing (conv3x3_kernel): the same epilogue -- the fp32 sum, ONE
+// rounding to half, then max(., 0) where relu -- of 16 consecutive pixels of channel n's row segment that begins at o;
+// the first `valid` of them exist.  wide: two 16-byte stores (o 16-byte aligned, valid 8 or 16), else element stores.
+__device__ __forceinline__ void ce_store_run(const f32x4* acc, float bias, __half* __restrict__ o, int valid, bool wide,
+                                             bool relu) {
+#pragma clang fp contract(off)  // as in ce_store
+  unsigned short h[16];
+#pragma unroll
+  for (int t = 0; t < 4; t++)
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const __half r = __float2half_rn(acc[t][i] + bias);
+      const float rf = __half2float(r);
+      h[4 * t + i] = (!relu || rf > 0.f || rf != rf) ? __half_as_ushort(r) : (unsigned short)0;
+    }
+  if (wide) {
+    uint4 v0, v1;
+    v0.x = h[0] | ((uint32_t)h[1] << 16); v0.y = h[2] | ((uint32_t)h[3] << 16);
+    v0.z = h[4] | ((uint32_t)h[5] << 16); v0.w = h[6] | ((uint32_t)h[7] << 16);
+    v1.x = h[8] | ((uint32_t)h[9] << 16); v1.y = h[10] | ((uint32_t)h[11] << 16);
+    v1.z = h[12] | ((uint32_t)h[13] << 16); v1.w = h[14] | ((uint32_t)h[15] << 16);
+    if (valid >= 8) reinterpret_cast<uint4*>(o)[0] = v0;
+    if (valid >= 16) reinterpret_cast<uint4*>(o)[1] = v1;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+      if (k < valid) o[k] = __ushort_as_half(h[k]);
   }
 }
 

@@ -55,6 +55,10 @@ void launch_motion_encode(const float* poses, const float* disps, const float* i
 // heads.hip
 void launch_update_heads(const void* const* x, const void* const* packed, void* const* out, const int* n_out,
                          const int* act, int heads, int B, int H, int W, hipStream_t s);
+// conv3x3.hip
+void launch_conv3x3(const void* x, const void* packed, void* y, int B, int c_in, int c_out, int H, int W,
+                    int64_t x_batch_stride, int64_t y_batch_stride, int64_t y_group_stride, int group_channels, int relu,
+                    hipStream_t s);
 // upsample.hip
 void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
                          bool half_mask, hipStream_t s);

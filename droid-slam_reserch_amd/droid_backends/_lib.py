@@ -97,6 +97,13 @@ ABI_HEADS = {
     "droid_update_heads": ("i", "3P 2I 5i p"),
 }
 SYMBOLS_HEADS = list(ABI_HEADS)
+# include/droid_conv3x3_hip.h, contract and prototypes (tests/test_conv3x3_abi.py holds the table against them).  A table
+# of its own again: tests/test_update_heads_abi.py pins ABI_HEADS at its two entries.
+ABI_CONV3X3 = {
+    "droid_conv3x3_packed_bytes": ("z", "2i"),
+    "droid_conv3x3": ("i", "3p 5i 3l 2i p"),
+}
+SYMBOLS_CONV3X3 = list(ABI_CONV3X3)
 # The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
 # A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
 # prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
@@ -112,9 +119,9 @@ _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": cty
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS or ABI_TEST as ctypes
-    types."""
-    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS):
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3 or
+    ABI_TEST as ctypes types."""
+    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3):
         if name in table:
             break
     else:
@@ -143,7 +150,8 @@ def load() -> ctypes.CDLL:
             "(python -c 'import __graft_entry__ as g; g.build()' or droid-slam_reserch_amd/csrc/build.sh). "
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_HEADS + SYMBOLS_TEST:
+    for s in (SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_HEADS + SYMBOLS_CONV3X3
+              + SYMBOLS_TEST):
         if not hasattr(lib, s):
             if s in SYMBOLS_TEST:
                 continue
