@@ -10,6 +10,7 @@
 
 #include "../../include/droid_backends_hip.h"
 #include "../../include/droid_conv3x3_hip.h"
+#include "../../include/droid_gru_hip.h"
 #include "../../include/droid_test_hooks_hip.h"
 #include "../../include/droid_heads_hip.h"
 #include "../../include/droid_motion_encode_hip.h"
@@ -1053,6 +1054,126 @@ int droid_conv3x3(const void* x, const void* packed, void* y, int B, int c_in, i
   launch_conv3x3(x, packed, y, B, c_in, c_out, H, W, x_batch_stride, y_batch_stride, y_group_stride, group_channels, relu,
                  (hipStream_t)stream);
   return check_hip("conv3x3");
+}
+
+// ---------------------------------------------------------------------------- conv_gru (droid_gru_hip.h)
+static bool gru_c_in_ok(int c_in) { return c_in >= 160 && c_in <= 512 && c_in % 32 == 0; }
+static bool gru_map_ok(int H, int W) { return H >= 1 && W >= 1 && (int64_t)H * W <= ((int64_t)1 << 30); }
+
+size_t droid_gru_packed_bytes(int c_in) { return gru_c_in_ok(c_in) ? gru_packed_bytes(c_in) : 0; }
+
+size_t droid_gru_workspace_bytes(int B, int H, int W) {
+  if (B < 0 || B > 65535 || !gru_map_ok(H, W)) return 0;
+  return gru_workspace_bytes(B, H, W);
+}
+
+// the size checks every segment call shares, in the header's order; *c_in_out = the channel sum
+static int gru_check_sizes(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg, int B,
+                           int H, int W, int* c_in_out) {
+  if (B < 0 || B > 65535) return fail(DROID_E_ARG, "conv_gru: bad %s", "B (0 .. 65535)");
+  if (nseg < 2 || nseg > 5) return fail(DROID_E_ARG, "conv_gru: bad %s", "nseg (2 .. 5)");
+  if (!seg || !seg_batch_stride || !seg_channels)
+    return fail(DROID_E_ARG, "conv_gru: null %s", "array (seg, seg_batch_stride, seg_channels)");
+  int c_in = 0;
+  for (int k = 0; k < nseg; k++) {
+    if (seg_channels[k] < 32 || seg_channels[k] > 512 || seg_channels[k] % 32 != 0 || (k == 0 && seg_channels[k] != 128))
+      return fail(DROID_E_ARG, "conv_gru: bad seg_channels[%d] (a positive multiple of 32; seg_channels[0] is 128)", k);
+    c_in += seg_channels[k];
+  }
+  if (!gru_c_in_ok(c_in)) return fail(DROID_E_ARG, "conv_gru: bad %s", "c_in (the channel sum, a multiple of 32 in 160 .. 512)");
+  if (!gru_map_ok(H, W)) return fail(DROID_E_ARG, "conv_gru: bad %s", "map size (H, W >= 1, H * W <= 2^30)");
+  const int64_t HW = (int64_t)H * W;
+  for (int k = 0; k < nseg; k++)
+    if (B > 1 && seg_batch_stride[k] < seg_channels[k] * HW)
+      return fail(DROID_E_ARG, "conv_gru: bad seg_batch_stride[%d] (below seg_channels * H * W)", k);
+  *c_in_out = c_in;
+  return DROID_OK;
+}
+
+static bool gru_null_segment(const void* const* seg, int nseg) {
+  for (int k = 0; k < nseg; k++)
+    if (!seg[k]) return true;
+  return false;
+}
+
+int droid_gru_context(const void* net, int64_t net_batch_stride, const void* packed, int c_in, int B, int H, int W, float* g,
+                      void* ws, size_t ws_bytes, void* stream) {
+  if (B < 0 || B > 65535) return fail(DROID_E_ARG, "conv_gru: bad %s", "B (0 .. 65535)");
+  if (!gru_c_in_ok(c_in)) return fail(DROID_E_ARG, "conv_gru: bad %s", "c_in (the channel sum, a multiple of 32 in 160 .. 512)");
+  if (!gru_map_ok(H, W)) return fail(DROID_E_ARG, "conv_gru: bad %s", "map size (H, W >= 1, H * W <= 2^30)");
+  if (B > 1 && net_batch_stride < 128 * (int64_t)H * W)
+    return fail(DROID_E_ARG, "conv_gru: bad %s", "net_batch_stride (below 128 * H * W)");
+  if (ws_bytes < gru_context_workspace_bytes(B, H, W))
+    return fail(DROID_E_ARG, "conv_gru: %s", "ws_bytes is below B * ceil(H * W / 256) * 512");
+  if (B == 0) return DROID_OK;
+  if (!net || !packed || !g || !ws) return fail(DROID_E_ARG, "conv_gru: null %s", "pointer (net, packed, g, ws)");
+  if ((((uintptr_t)packed | (uintptr_t)ws) & 15) != 0) return fail(DROID_E_ARG, "conv_gru: %s", "packed or ws is not 16-byte aligned");
+  launch_gru_context(net, net_batch_stride, packed, c_in, B, H, W, g, ws, (hipStream_t)stream);
+  return check_hip("conv_gru");
+}
+
+int droid_gru_gates(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg,
+                    const void* packed, const float* g, void* z, void* rnet, int B, int H, int W, void* stream) {
+  int c_in = 0;
+  if (int rc = gru_check_sizes(seg, seg_batch_stride, seg_channels, nseg, B, H, W, &c_in)) return rc;
+  if (B == 0) return DROID_OK;
+  if (gru_null_segment(seg, nseg) || !packed || !g || !z || !rnet)
+    return fail(DROID_E_ARG, "conv_gru: null %s", "pointer (seg[k], packed, g, z, rnet)");
+  if (((uintptr_t)packed & 15) != 0) return fail(DROID_E_ARG, "conv_gru: %s", "packed is not 16-byte aligned");
+  launch_gru_gates(seg, seg_batch_stride, seg_channels, nseg, packed, g, z, rnet, B, H, W, (hipStream_t)stream);
+  return check_hip("conv_gru");
+}
+
+int droid_gru_update(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg,
+                     const void* packed, const float* g, const void* z, const void* net, int64_t net_batch_stride,
+                     void* out, int64_t out_batch_stride, int B, int H, int W, void* stream) {
+  int c_in = 0;
+  if (int rc = gru_check_sizes(seg, seg_batch_stride, seg_channels, nseg, B, H, W, &c_in)) return rc;
+  if (B > 1 && net_batch_stride < 128 * (int64_t)H * W)
+    return fail(DROID_E_ARG, "conv_gru: bad %s", "net_batch_stride (below 128 * H * W)");
+  if (B > 1 && out_batch_stride < 128 * (int64_t)H * W)
+    return fail(DROID_E_ARG, "conv_gru: bad %s", "out_batch_stride (below 128 * H * W)");
+  if (B == 0) return DROID_OK;
+  if (gru_null_segment(seg, nseg) || !packed || !g || !z || !net || !out)
+    return fail(DROID_E_ARG, "conv_gru: null %s", "pointer (seg[k], packed, g, z, net, out)");
+  if (((uintptr_t)packed & 15) != 0) return fail(DROID_E_ARG, "conv_gru: %s", "packed is not 16-byte aligned");
+  launch_gru_update(seg, seg_batch_stride, seg_channels, nseg, packed, g, z, net, net_batch_stride, out, out_batch_stride, B, H,
+                    W, (hipStream_t)stream);
+  return check_hip("conv_gru");
+}
+
+int droid_conv_gru(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg,
+                   const void* packed, void* out, int64_t out_batch_stride, int B, int H, int W, void* ws, size_t ws_bytes,
+                   void* stream) {
+  int c_in = 0;
+  if (int rc = gru_check_sizes(seg, seg_batch_stride, seg_channels, nseg, B, H, W, &c_in)) return rc;
+  if (B > 1 && out_batch_stride < 128 * (int64_t)H * W)
+    return fail(DROID_E_ARG, "conv_gru: bad %s", "out_batch_stride (below 128 * H * W)");
+  if (ws_bytes < gru_workspace_bytes(B, H, W)) return fail(DROID_E_ARG, "conv_gru: %s", "ws_bytes is below droid_gru_workspace_bytes");
+  if (B == 0) return DROID_OK;
+  if (gru_null_segment(seg, nseg) || !packed || !out || !ws)
+    return fail(DROID_E_ARG, "conv_gru: null %s", "pointer (seg[k], packed, out, ws)");
+  if ((((uintptr_t)packed | (uintptr_t)ws) & 15) != 0) return fail(DROID_E_ARG, "conv_gru: %s", "packed or ws is not 16-byte aligned");
+  // ws: the context partials, g [B,3,128] fp32, z, rnet [B,128,H,W] half
+  char* base = static_cast<char*>(ws);
+  float* g = reinterpret_cast<float*>(base + gru_context_workspace_bytes(B, H, W));
+  char* z = reinterpret_cast<char*>(g) + (size_t)B * 3 * 128 * sizeof(float);
+  const size_t plane = (gru_workspace_bytes(B, H, W) - (size_t)(z - base)) / 2;
+  char* rnet = z + plane;
+  hipStream_t s = (hipStream_t)stream;
+  launch_gru_context(seg[0], seg_batch_stride[0], packed, c_in, B, H, W, g, ws, s);
+  launch_gru_gates(seg, seg_batch_stride, seg_channels, nseg, packed, g, z, rnet, B, H, W, s);
+  const void* seg_q[5];
+  int64_t stride_q[5];
+  for (int k = 0; k < nseg; k++) {
+    seg_q[k] = seg[k];
+    stride_q[k] = seg_batch_stride[k];
+  }
+  seg_q[0] = rnet;
+  stride_q[0] = 128 * (int64_t)H * W;
+  launch_gru_update(seg_q, stride_q, seg_channels, nseg, packed, g, z, seg[0], seg_batch_stride[0], out, out_batch_stride, B, H,
+                    W, s);
+  return check_hip("conv_gru");
 }
 
 }  // extern "C"

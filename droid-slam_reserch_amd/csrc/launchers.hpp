@@ -59,6 +59,17 @@ void launch_update_heads(const void* const* x, const void* const* packed, void* 
 void launch_conv3x3(const void* x, const void* packed, void* y, int B, int c_in, int c_out, int H, int W,
                     int64_t x_batch_stride, int64_t y_batch_stride, int64_t y_group_stride, int group_channels, int relu,
                     hipStream_t s);
+// gru.hip (include/droid_gru_hip.h: the arguments under their names there)
+size_t gru_packed_bytes(int c_in);
+size_t gru_context_workspace_bytes(int B, int H, int W);
+size_t gru_workspace_bytes(int B, int H, int W);
+void launch_gru_context(const void* net, int64_t net_batch_stride, const void* packed, int c_in, int B, int H, int W,
+                        float* g, void* ws, hipStream_t s);
+void launch_gru_gates(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg,
+                      const void* packed, const float* g, void* z, void* rnet, int B, int H, int W, hipStream_t s);
+void launch_gru_update(const void* const* seg, const int64_t* seg_batch_stride, const int* seg_channels, int nseg,
+                       const void* packed, const float* g, const void* z, const void* net, int64_t net_batch_stride,
+                       void* out, int64_t out_batch_stride, int B, int H, int W, hipStream_t s);
 // upsample.hip
 void launch_cvx_upsample(const float* data, const int64_t* ix, const void* mask, float* out, int n, int nbuf, int H, int W,
                          bool half_mask, hipStream_t s);

@@ -26,6 +26,7 @@ from .corr_encode import CorrEncoder
 from .motion_encode import FlowEncoder
 from .update_heads import UpdateHeads
 from .conv3x3 import Conv3x3
+from .conv_gru import ConvGRU
 
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_forward",
            "altcorr_backward", "corr_index_forward", "corr_index_backward",
@@ -41,7 +42,8 @@ __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "altcorr_
            "CorrEncoder",                      # the lookup fused with corr_encoder[0:2] (droid_backends.corr_encode)
            "FlowEncoder",                      # reproject + motion features fused with flow_encoder[0:2] (droid_backends.motion_encode)
            "UpdateHeads",                      # the last layers of delta, weight and eta in one launch each (droid_backends.update_heads)
-           "Conv3x3"]                          # the 3 x 3 convolutions + ReLU in between, on the f16 matrix cores (droid_backends.conv3x3)
+           "Conv3x3",                          # the 3 x 3 convolutions + ReLU in between, on the f16 matrix cores (droid_backends.conv3x3)
+           "ConvGRU"]                          # the ConvGRU in four launches, its inputs read where they lie (droid_backends.conv_gru)
 # droid_backends.pyramid_store (SlotTable, PyramidStore): the capacity buffers behind `self.corr` of a factor graph
 
 _DT = {torch.float16: _lib.DROID_F16, torch.float32: _lib.DROID_F32, torch.float64: _lib.DROID_F64}

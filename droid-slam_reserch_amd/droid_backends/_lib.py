@@ -104,6 +104,18 @@ ABI_CONV3X3 = {
     "droid_conv3x3": ("i", "3p 5i 3l 2i p"),
 }
 SYMBOLS_CONV3X3 = list(ABI_CONV3X3)
+# include/droid_gru_hip.h, contract and prototypes (tests/test_conv_gru_abi.py holds the table against them).  A table of
+# its own: tests/test_conv3x3_abi.py pins ABI_CONV3X3 at its two entries.  The segment table of a call is "P" (the
+# pointers), "L" (const int64_t*: the batch strides) and "I" (the channels).
+ABI_GRU = {
+    "droid_gru_packed_bytes": ("z", "i"),
+    "droid_gru_workspace_bytes": ("z", "3i"),
+    "droid_gru_context": ("i", "p l p 4i 2p z p"),
+    "droid_gru_gates": ("i", "P L I i 4p 3i p"),
+    "droid_gru_update": ("i", "P L I i 4p l p l 3i p"),
+    "droid_conv_gru": ("i", "P L I i 2p l 3i p z p"),
+}
+SYMBOLS_GRU = list(ABI_GRU)
 # The test hooks, include/droid_test_hooks_hip.h (tests/test_gpu_lin_pinned.py holds the table against the prototypes).
 # A table and a header of their own: the main header is the drop-in boundary and tests/test_abi.py pins its 48
 # prototypes, so a hook that only the tests need is not added there.  load() binds a hook where the library exports it
@@ -115,13 +127,13 @@ ABI_TEST = {
 SYMBOLS_TEST = list(ABI_TEST)
 _CTYPE = {"i": ctypes.c_int, "l": ctypes.c_int64, "z": ctypes.c_size_t, "f": ctypes.c_float, "d": ctypes.c_double,
           "p": ctypes.c_void_p, "P": ctypes.POINTER(ctypes.c_void_p), "I": ctypes.POINTER(ctypes.c_int),
-          "Z": ctypes.POINTER(ctypes.c_size_t), "s": ctypes.c_char_p}
+          "Z": ctypes.POINTER(ctypes.c_size_t), "s": ctypes.c_char_p, "L": ctypes.POINTER(ctypes.c_int64)}
 
 
 def signature(name):
-    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3 or
-    ABI_TEST as ctypes types."""
-    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3):
+    """(restype, argtypes) of an entry of ABI, ABI_UPDATE, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3, ABI_GRU
+    or ABI_TEST as ctypes types."""
+    for table in (ABI, ABI_TEST, ABI_CORR_ENCODE, ABI_MOTION_ENCODE, ABI_HEADS, ABI_CONV3X3, ABI_GRU):
         if name in table:
             break
     else:
@@ -151,7 +163,7 @@ def load() -> ctypes.CDLL:
             "There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
     for s in (SYMBOLS + SYMBOLS_UPDATE + SYMBOLS_CORR_ENCODE + SYMBOLS_MOTION_ENCODE + SYMBOLS_HEADS + SYMBOLS_CONV3X3
-              + SYMBOLS_TEST):
+              + SYMBOLS_GRU + SYMBOLS_TEST):
         if not hasattr(lib, s):
             if s in SYMBOLS_TEST:
                 continue
